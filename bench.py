@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native MeTRAbs per-crop hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A *step* is one pass of the hot path over one internal batch of synthetic input that is already
 resident in HBM: BASELINE.json configs[1] = EfficientNetV2-S, 256 px crops, 64 crops per GPU,
@@ -19,9 +19,12 @@ replay of the captured internal batch that rounds 1-3 timed):
 Parenthesised stages are the hand-written HIP kernels of libmetrabs_hip.so.  Metric: crops/sec,
 whole job (all ranks).  Weak scaling: every rank processes its own 64 crops per step.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description) with two extra objects:
-``roofline`` for the dominant hand-written kernel of the step and ``cpu_baseline`` for the CPU
-restatement of the reference path (oracle/cpu_ref.py) timed on this box's host cores.
+Prints ONE JSON line on rank 0: metric, value (crops/s), unit, higher_is_better, dtype, ms_per_step (one
+timed step), steps, warmup and the workload.  A plain run does only that.  With --full the line also
+carries ``roofline`` for the dominant hand-written kernel of the step, ``cpu_baseline`` for the CPU
+restatement of the reference path (oracle/cpu_ref.py) timed on the host cores, and the other probes,
+variants and parity checks (null in a plain run).  --dump-outputs DIR writes the last timed step's
+result arrays as DIR/<name>.npy.
 """
 import argparse
 import copy
@@ -97,15 +100,25 @@ def parse_args():
                          '--graph-gather): a bare replay of the captured internal batch (GraphedCropPipeline)')
     ap.add_argument('--no-api-path', action='store_true',
                     help='skip the `api_path` probe (crops/s through Pose3dEstimator.estimate_poses_batched)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, run everything else the line can carry: per-kernel timing, '
+                         'roofline probes (with the rocprofv3 PMC passes), parity probe, API-vs-pipeline check, '
+                         'backbone / precision / depth variants and the CPU baseline.  Off by default: a plain run '
+                         'sets up, warms up, times the steps and prints the contract line (those fields null)')
     ap.add_argument('--quick', action='store_true',
-                    help='print the contract line only: no per-kernel timing, roofline probes, parity probe, '
-                         'backbone variants or CPU baseline (those fields are null)')
+                    help='the contract line only, even with --full (what a plain run prints anyway)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (poses3d, poses2d, ...) '
+                         'as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds can be '
+                         'compared output for output')
     ap.add_argument('--no-pmc', action='store_true',
                     help='do not run the two rocprofv3 --pmc passes that measure `roofline.traffic`')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-decode-roofline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.config in (2, 4):  # (explicit --backbone / --res / --batch still win when given)
         if args.backbone == 'effnetv2-s':
             args.backbone = 'effnetv2-l'
@@ -925,6 +938,37 @@ def parity_from_identical_crops(est, extras, cfg, args):
                      'in-scope part on identical features')
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(api_result, pipe, strong, shard_out, gathered):
+    """What the caller of the timed path received in the last step (rank 0's view): the API's poses,
+    concatenated over the frames, or the captured pipeline's output buffers; plus the all-gathered poses
+    of the job when the step ends in a collective."""
+    if api_result is not None:
+        out = {'poses3d': torch.cat(api_result['poses3d']), 'poses2d': torch.cat(api_result['poses2d'])}
+    elif strong:
+        out = {'poses3d': shard_out}
+    else:
+        out = {'poses3d': pipe.poses3d, 'poses2d': pipe.poses2d}
+    if gathered is not None:
+        out['poses3d_all_ranks'] = gathered
+    torch.cuda.synchronize()
+    return {k: v.detach().cpu().clone() for k, v in out.items()}
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy, float32 (float64 stays float64).  Over 64 MB in all, a fixed, seeded sample of rows."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(v.numel() * (8 if v.dtype == torch.float64 else 4) for v in arrays.values())
+    for name, v in arrays.items():
+        a = v.numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+        if total > DUMP_LIMIT_BYTES and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks here --
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -1004,7 +1048,7 @@ def main():
     pipe = GraphedCropPipeline(est, args.frames, im_h, im_w, n_box, num_aug=args.num_aug,
                                use_graph=not args.no_graph)
     synth_inputs(pipe, args.frames, im_h, im_w, n_box, seed=100 + rank)
-    pipe.capture()
+    full = args.full and not args.quick
 
     J = est.joint_info.n_joints
     # config 1 (weak scaling): one internal batch per rank and step.  config 2 (strong scaling): the
@@ -1012,6 +1056,16 @@ def main():
     # (metrabs_amd.distributed.shard_internal_batches -- the unit of multiperson_model.py:189-220);
     # a rank replays its graph once per batch it owns, then the poses of the step are all-gathered.
     strong = args.strong
+    # ---- the timed step of the weak-scaling configs goes through the drop-in API itself
+    step_mode = args.step
+    if step_mode == 'auto':
+        step_mode = 'pipeline' if (strong or args.graph_gather or args.no_graph) else 'api'
+    if step_mode == 'api' and strong:
+        raise SystemExit('--step api: the strong-scaling configs replay one captured internal batch per owned batch')
+    if step_mode == 'pipeline' or full:
+        # (the API step captures its own graphs: the bare pipeline is timed, or compared against and probed
+        #  by --full)
+        pipe.capture()
     if strong:
         total_boxes = args.total_crops // args.num_aug
         my_batches = len(distributed.shard_internal_batches(total_boxes, n_box, rank, world))
@@ -1036,13 +1090,9 @@ def main():
             pipe.capture()
             gather_mode += f' [--graph-gather failed: {str(e)[:120]}]'
 
-    # ---- the timed step of the weak-scaling configs goes through the drop-in API itself
-    step_mode = args.step
-    if step_mode == 'auto':
-        step_mode = 'pipeline' if (strong or args.graph_gather or args.no_graph) else 'api'
-    if step_mode == 'api' and strong:
-        raise SystemExit('--step api: the strong-scaling configs replay one captured internal batch per owned batch')
     api_call = None
+    api_last = [None]   # the API's return value of the latest call (--dump-outputs)
+    api_vs_pipeline_max_mm = None
     if step_mode == 'api':
         per_frame = [int((pipe.image_ids == i).sum()) for i in range(args.frames)]
         order = torch.argsort(pipe.image_ids.long(), stable=True)   # the API takes boxes frame by frame
@@ -1062,14 +1112,16 @@ def main():
             frames_now = frame_sets[api_turn[0] % len(frame_sets)]
             api_turn[0] += 1
             res = est.estimate_poses_batched(frames_now, api_boxes, **api_kw)
+            api_last[0] = res
             return torch.cat(res['poses3d'])
 
         with torch.inference_mode():
             first = api_call()
-            # the API's internal batch is the pipeline's: same kernels, same shapes, same box order (synth_inputs
-            # lays the boxes out frame by frame) -- the difference is reported in the line, 0.0 expected
-            want = pipe.run()[order]
-            api_vs_pipeline_max_mm = float((first - want).abs().max())
+            if full:
+                # the API's internal batch is the pipeline's: same kernels, same shapes, same box order (synth_inputs
+                # lays the boxes out frame by frame) -- the difference is reported in the line, 0.0 expected
+                want = pipe.run()[order]
+                api_vs_pipeline_max_mm = float((first - want).abs().max())
             if not torch.isfinite(first).all():
                 raise SystemExit('bench: non-finite poses from the API step')
 
@@ -1109,6 +1161,8 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(api_last[0], pipe, strong, shard_out, gathered))
     multi = None
     if collective:
         # every rank's own time for the K steps (one line must be enough to diagnose a flat curve),
@@ -1206,9 +1260,9 @@ def main():
     }
     if multi is not None:
         out['multi_gpu'] = multi
-    if args.quick:
+    if not full:
         out.update(roofline=None, cpu_baseline=None,
-                   note='--quick: the contract line only (no per-kernel timing, probes or baselines)')
+                   note='the contract line only (per-kernel timing, probes, variants and baselines: --full)')
     else:
         try:
             out.update(analysis(args, est, cfg, pipe, dev, elapsed / args.steps, im_h, im_w, n_box, world))

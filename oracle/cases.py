@@ -369,6 +369,44 @@ def box_consistency_kat():
     return pose[None].repeat(len(rows), 1, 1), boxes, want
 
 
+# ---- inputs of the recorded reference pins (tests/golden/oracle_pins.npz, oracle/gen_golden.py:gen_pins)
+PIN_HEAD_BATCHES = [(7, 17, 8, 8, 256), (3, 29, 12, 8, 384), (2, 5, 4, 3, 128)]   # (B, J, H, D, proc_side)
+
+
+def pin_head_batch(seed):
+    """Random logits [B, J * (1 + D), H, H] and intrinsics of PIN_HEAD_BATCHES[seed] -> (logits, K, cfg)."""
+    B, J, H, D, P = PIN_HEAD_BATCHES[seed]
+    g = gen(900 + seed)
+    cfg = HeadConfig(proc_side=P, depth=D)
+    logits = torch.randn(B, J * (1 + D), H, H, generator=g) * 2
+    K = torch.tensor([[500.0, 0, P / 2], [0, 510.0, P / 2], [0, 0, 1]]).repeat(B, 1, 1)
+    return logits, K, cfg
+
+
+def pin_box_consistency_inputs():
+    """{'kat': box_consistency_kat's poses and boxes, 'random': 200 random poses and boxes}."""
+    pose2d, boxes, _ = box_consistency_kat()
+    g = gen(55)
+    p = torch.rand(200, 17, 2, generator=g) * 300
+    b = torch.cat([torch.rand(200, 2, generator=g) * 200, 50 + torch.rand(200, 2, generator=g) * 250,
+                   torch.ones(200, 1)], dim=1)
+    return {'kat': (pose2d, boxes), 'random': (p, b)}
+
+
+def pin_geometry_inputs():
+    """Points and distortion coefficients for distort / undistort_points, (forward, up) pairs for
+    lookat_matrix (the second has forward parallel to up for its first row: the fallback branch)."""
+    g = gen(77)
+    pts = torch.randn(4, 5, 2, generator=g) * 0.4
+    coeffs = [torch.zeros(4, 5), torch.tensor([DISTORTION_5] * 4), torch.tensor([DISTORTION_12] * 4)]
+    fwd = torch.randn(6, 3, generator=g)
+    fwd2 = fwd.clone()
+    fwd2[0] = torch.tensor([0.0, 0.0, 2.0])
+    lookat = [(fwd, torch.tensor([[0.0, -1.0, 0.0]]).repeat(6, 1)),
+              (fwd2, torch.tensor([[0.0, 0.0, 1.0]]).repeat(6, 1))]
+    return dict(points=pts, coeffs=coeffs, lookat=lookat)
+
+
 def synth_images(n, h, w, seed):
     """uint8 [n,3,h,w]: even images are uniform noise (worst case for bilinear rounding), odd
     images are smooth gradients + mild noise."""

@@ -320,6 +320,63 @@ def gen_backbone(ref):
              shapes=np.array([','.join(map(str, v.shape)) for v in sd.values()]), output=y)
 
 
+def gen_backbone_probe(ref):
+    """tests/test_loading.py: the reference's EfficientNetV2-S stack on cases.deterministic_state(seed=3), one
+    160 x 128 frame, with and without the centered stride, and the keys of its state dict."""
+    x = torch.rand(1, 3, 128, 160, generator=cases.gen(4))
+    out = {}
+    for tag, centered in (('centered', True), ('uncentered', False)):
+        with rh.config(centered_stride=centered):
+            stack = torch.nn.Sequential(ref.efficientnet.PreprocLayer(),
+                                        ref.efficientnet.efficientnet_v2_s().features).eval()
+        state = cases.deterministic_state(stack.state_dict(), seed=3)
+        stack.load_state_dict(state)
+        with torch.inference_mode():
+            out[f'output_{tag}'] = stack(x)
+    save('backbone_effnetv2_s_probe', keys=np.array(list(state)), input_sha256=np.array(cases.sha256_of(x)), **out)
+
+
+def gen_pins(ref):
+    """tests/test_oracle_pin.py:TestAgainstLiveReference: the reference functions' outputs on the inputs that
+    test builds (heads + reconstruct_absolute on random batches, batch coupling, the weak-perspective branch,
+    box consistency, geometry helpers)."""
+    from oracle import cpu_ref
+    out = {}
+    for seed, (B, J, H, D, P) in enumerate(cases.PIN_HEAD_BATCHES):
+        logits, K, cfg = cases.pin_head_batch(seed)
+        with rh.config(**cfg.as_dict()), torch.inference_mode():
+            heads = ref.metrabs_model.MetrabsHeads(n_points=J).eval()
+            heads.conv_final = torch.nn.Identity()
+            r2d, r3d = heads(logits)
+            out[f'heads{seed}_coords2d'], out[f'heads{seed}_coords3d_rel'] = r2d, r3d
+            out[f'heads{seed}_poses3d'] = ref.ptu3d.reconstruct_absolute(r2d, r3d, K, mix_3d_inside_fov=0.5)
+        out[f'heads{seed}_input_sha256'] = np.array(cases.sha256_of(logits, K))
+    c2d, rel, K, cfg = cases.recon_case('b64_j17')
+    with rh.config(**cfg.as_dict()), torch.inference_mode():
+        out['coupling_full'] = ref.ptu3d.reconstruct_absolute(c2d, rel, K, mix_3d_inside_fov=0.5)
+        out['coupling_one'] = ref.ptu3d.reconstruct_absolute(c2d[:1], rel[:1], K[:1], mix_3d_inside_fov=0.5)
+    weak = {'b8': cases.recon_case('b8_weak'),
+            'kat': cases.weak_perspective_kat()[:3] + (cpu_ref.HeadConfig(weak_perspective=True),)}
+    for tag, (c2d, rel, K, cfg) in weak.items():
+        with rh.config(**cfg.as_dict()), torch.inference_mode(), rh.weak_perspective_runnable(ref):
+            out[f'weak_{tag}'] = rh.plain(ref.ptu3d.reconstruct_absolute(c2d, rel, K, mix_3d_inside_fov=0.5,
+                                                                         weak_perspective=True))
+    for tag, (pose2d, boxes) in cases.pin_box_consistency_inputs().items():
+        out[f'box_{tag}'] = rh.plain(ref.plausibility_check.is_pose_consistent_with_box(
+            rh.minmax_values(pose2d), boxes))
+    g = cases.pin_geometry_inputs()
+    for i, coeffs in enumerate(g['coeffs']):
+        out[f'distort_{i}'] = ref.warping.distort_points(g['points'], coeffs)
+        out[f'undistort_{i}'] = ref.warping.undistort_points(g['points'], coeffs)
+    for i, (fwd, up) in enumerate(g['lookat']):
+        out[f'lookat_{i}'] = ref.ptu3d.lookat_matrix(fwd, up)
+    out['intrinsic_fov55_480x640'] = ref.ptu3d.intrinsic_matrix_from_field_of_view(55, (480, 640))
+    for n in (1, 2, 5):
+        for ep in (True, False):
+            out[f'linspace_{n}_{int(ep)}'] = ref.ptu.linspace(0.8, 1.0, n, endpoint=ep)
+    save('oracle_pins', **out)
+
+
 def gen_tta(ref):
     """TTA parameter tables computed by the reference's own expressions:
     run _estimate_poses_batched with a recording stub for _predict_in_batches."""
@@ -430,7 +487,7 @@ def main():
     ref = rh.load()
     groups = dict(heads=gen_heads, headconv=gen_headconv, recon=gen_recon, warp=gen_warp,
                   tta=gen_tta, e2e=gen_e2e, latent=gen_latent, detpre=gen_detpre, filter=gen_filter, backbone=gen_backbone,
-                  parity=gen_parity, jitter=gen_jitter)
+                  backbone_probe=gen_backbone_probe, pins=gen_pins, parity=gen_parity, jitter=gen_jitter)
     for name in (sys.argv[1:] or [g for g in groups if g != 'jitter']):
         if ':' in name:  # one case of a group (recon, e2e: their lstsq goldens carry run-to-run jitter)
             group, only = name.split(':', 1)

@@ -181,6 +181,35 @@ def test_bench_cli_contract_and_kernel_naming(monkeypatch):
     assert bench.head_kernel_name(64, 64, 17, 8, 'f16', 1283).startswith('library')      # C % 8 != 0
 
 
+def test_bench_full_and_dump_outputs_flags(monkeypatch, tmp_path):
+    """bench.py: the probes and baselines only with --full; --dump-outputs DIR writes float32 (float64 stays
+    float64) .npy files, a fixed sample of rows when the arrays exceed 64 MB in all."""
+    import importlib
+    import sys
+    bench = importlib.import_module('bench')
+    monkeypatch.setattr(sys, 'argv', ['bench.py'])
+    a = bench.parse_args()
+    assert not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path), '--steps', '3'])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == str(tmp_path) and a.steps == 3
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    p3 = torch.randn(64, 17, 3, dtype=torch.float16)
+    d64 = torch.randn(5, 2, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'small'), {'poses3d': p3, 'd': d64})
+    got = np.load(tmp_path / 'small' / 'poses3d.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, p3.float().numpy())
+    assert np.load(tmp_path / 'small' / 'd.npy').dtype == np.float64
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 1000)
+    big = torch.arange(400 * 3, dtype=torch.float32).reshape(400, 3)
+    bench.dump_outputs(str(tmp_path / 'a'), {'x': big})
+    bench.dump_outputs(str(tmp_path / 'b'), {'x': big})
+    a1, b1 = np.load(tmp_path / 'a' / 'x.npy'), np.load(tmp_path / 'b' / 'x.npy')
+    assert a1.nbytes <= 1000 and a1.shape[1] == 3 and np.array_equal(a1, b1)   # the same sample every time
+
+
 def test_head_plan_follows_the_measured_model():
     """mtr_head_plan (host-only): the launch plan of the f32 head reproduces the measured best choice of
     the round-3 sweeps (profiles/r03*_head_sweep.jsonl, r03f_head_plan_check.jsonl) on their shapes."""
