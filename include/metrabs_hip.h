@@ -495,6 +495,17 @@ int mtr_depthwise3x3_bias_act_padded(const void* x, int dtype, const float* weig
                                      int pad_left, int pad_bottom, int pad_right, void* y,
                                      float* row_mean, mtr_stream_t stream);
 
+/* K12 (outside the reference's hot path, like K10): the squeeze-excite gate of an MBConv block
+ * (efficientnet.py:110-173, torchvision SqueezeExcitation) in one launch, from the [B, C] f32 channel
+ * mean K10 / K11 emit:
+ *   gate[b, c] = gate_fn(b2[c] + sum_s w2[c, s] * act(b1[s] + sum_k w1[s, k] * mean[b, k]))
+ * w1 [S, C], w2 [C, S] (the fc1 / fc2 1x1 convolution weights), b1 [S], b2 [C], all f32, contiguous;
+ * mean and w1 16-byte aligned, C a multiple of 4.  act: as mtr_bias_act_nchw; gate_fn: 0 sigmoid,
+ * 1 hardsigmoid (torch.nn.Hardsigmoid).  f32 arithmetic in a fixed order, no atomics. */
+int mtr_se_gate(const float* mean /*[B*C]*/, const float* w1, const float* b1, const float* w2,
+                const float* b2, int act, int gate_fn, int B, int C, int S, float* gate /*[B*C]*/,
+                mtr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p]),
     'mtr_bias_act_nchw': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int,
                                   c_int, c_void_p]),
+    'mtr_se_gate': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                            c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

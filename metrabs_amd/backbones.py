@@ -70,13 +70,31 @@ class SqueezeExcite(nn.Module):
     # epilogue pass also produced the per-channel mean of the tensor it handed over
     mean_from = ()
 
+    _GATE_NAMES = {nn.Sigmoid: 'sigmoid', nn.Hardsigmoid: 'hardsigmoid'}
+
     def forward(self, x):
-        s = None
+        mean = None
         for src in self.mean_from:
-            s = src.take_mean(x)
+            mean = src.take_mean_f32(x)
+        if mean is not None and self._fused_gate_ok():
+            # fc1, + b1, act, fc2, + b2, gate as ONE HIP launch from the f32 mean (K12)
+            from . import kernels
+            g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                                _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)])
+            return x * g.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
+        s = None if mean is None else mean.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         if s is None:
             s = x.mean((2, 3), keepdim=True)
         return x * self.gate(self.fc2(self.act(self.fc1(s))))
+
+    def _fused_gate_ok(self):
+        """K12 computes no gradient: only where none is wanted, for the layer types it implements."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return False
+        return (type(self.act) in (nn.SiLU, nn.ReLU) and type(self.gate) in self._GATE_NAMES
+                and self.fc1.weight.dtype == torch.float32 and self.fc1.bias is not None
+                and self.fc2.bias is not None and self.fc1.weight.is_cuda
+                and self.fc1.in_channels % 4 == 0)
 
 
 def _padded_conv(layers, name, cin, cout, k, stride, groups=1, act=nn.SiLU, bottomright=False):
@@ -267,12 +285,17 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
 
-    def take_mean(self, x):
-        """The [B, C, 1, 1] mean of `x` if `x` is the very tensor this module returned last."""
+    def take_mean_f32(self, x):
+        """The [B, C] f32 mean of `x` if `x` is the very tensor this module returned last."""
         held, self._mean = self._mean, None
         if held is not None and held[0] is x:
-            return held[1].to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
+            return held[1]
         return None
+
+    def take_mean(self, x):
+        """The [B, C, 1, 1] mean of `x` (in x's dtype) if `x` is the very tensor this module returned last."""
+        m = self.take_mean_f32(x)
+        return None if m is None else m.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
 
     def forward(self, x, residual=None):
         y = self.conv(x)
@@ -320,6 +343,7 @@ class DepthwiseBiasAct(nn.Module):
                 and conv.padding_mode == 'zeros')
 
     take_mean = ConvBiasAct.take_mean
+    take_mean_f32 = ConvBiasAct.take_mean_f32
 
     def forward(self, x):
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]

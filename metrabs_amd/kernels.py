@@ -624,3 +624,27 @@ def depthwise3x3_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
         ACT_CODES[act], B, C, H, W, int(stride), pt, pl, pb, pr, _ptr(y), None if mean is None else _ptr(mean),
         current_stream_ptr(x.device)), 'mtr_depthwise3x3_bias_act_padded')
     return (y, mean) if want_mean else y
+
+
+# K12: the squeeze-excite gate of an MBConv block (csrc/se.hip)
+
+SE_GATE_CODES = {'sigmoid': 0, 'hardsigmoid': 1}
+
+
+def se_gate(mean, w1, b1, w2, b2, act, gate_fn, out=None):
+    """gate [B, C] f32 = gate_fn(w2 . act(w1 . mean + b1) + b2) in one launch: the squeeze-excite block
+    of an MBConv from the [B, C] f32 channel mean K10 / K11 emit (instead of PyTorch-ROCm's fc1 GEMM,
+    bias, activation, fc2 GEMM, bias and gate kernels).  w1 [S, C] (or the [S, C, 1, 1] conv weight),
+    w2 [C, S], b1 [S], b2 [C]; all f32.  act: a key of ACT_CODES, gate_fn: 'sigmoid' / 'hardsigmoid'."""
+    require_cuda(mean, w1, b1, w2, b2)
+    B, C = mean.shape[0], mean.shape[1]
+    S = w1.shape[0]
+    w1, w2 = w1.reshape(S, -1), w2.reshape(C, -1)
+    if mean.dtype != torch.float32 or mean.numel() != B * C or w1.shape[1] != C or w2.shape[1] != S:
+        raise ValueError('se_gate: mean [B, C] f32, w1 [S, C], w2 [C, S]')
+    tensors = [t.contiguous().float() for t in (mean, w1, b1, w2, b2)]
+    if out is None:
+        out = torch.empty(B, C, device=mean.device, dtype=torch.float32)
+    check(_lib.load().mtr_se_gate(*(_ptr(t) for t in tensors), ACT_CODES[act], SE_GATE_CODES[gate_fn], B, C, S,
+                                  _ptr(out), current_stream_ptr(mean.device)), 'mtr_se_gate')
+    return out

@@ -1,0 +1,223 @@
+#!/usr/bin/env python
+"""Per-layer kernel times of ONE backbone forward at the bench shape, attributed to blocks and roles.
+
+    # on the GPU: record a marked forward under the kernel tracer
+    rocprofv3 --kernel-trace --output-format csv -d OUT/trace -o bb -- \\
+        python tools/backbone_trace.py record --markers OUT/markers.json
+    # anywhere: the table
+    python tools/backbone_trace.py report --trace OUT/trace --markers OUT/markers.json --out TABLE.md
+
+`record` builds the backbone of bench.py's configs[1] the way bench.py:build_model does (EfficientNetV2-S,
+batch norm calibrated on the sampler's crops, fold_batchnorm(fused_epilogue=True), f32, the deterministic
+convolution pin of Metrabs.deterministic_backbone), runs a few unmarked forwards at batch 64 / 256 px and
+then one forward in which a forward pre-hook on every module first launches a marker kernel
+(torch.cuda._sleep(0), `spin_kernel`).  The kernels between two markers belong to the module entered
+last; `report` names each kernel's role in its block (SE fc1 / bias / act, fc2, gate, mul, project,
+K10, K11, se_gate, ...) from that module and the kernel's name and writes a markdown table: per MBConv
+block the time of every role, the sum of the squeeze-excite tail, and per project shape the GEMM time.
+Marker kernels and the gaps they open are not counted; kernel durations are the tracer's.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import re
+import sys
+from collections import OrderedDict, defaultdict
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MARK = 'spin_kernel'
+
+
+def record(args):
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from metrabs_amd.backbones import build_backbone, calibrate_batchnorm, fold_batchnorm
+    dev = torch.device('cuda')
+    torch.manual_seed(1234)
+    torch.backends.cudnn.deterministic = True  # Metrabs.deterministic_backbone (on for f32)
+    net = build_backbone('effnetv2-s').to(dev)
+    calibrate_batchnorm(net, args.res, dev,
+                        samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
+    net = fold_batchnorm(net.eval(), fused_epilogue=True)
+    x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+    order = []
+
+    def hook(name):
+        def pre(mod, inp):
+            torch.cuda._sleep(0)
+            order.append(name)
+        return pre
+
+    with torch.inference_mode():
+        for _ in range(args.warmup):
+            net(x)
+        torch.cuda.synchronize()
+        handles = [m.register_forward_pre_hook(hook(n or '<root>')) for n, m in net.named_modules()]
+        feat = net(x)
+        torch.cuda.synchronize()
+        for h in handles:
+            h.remove()
+    shapes = {}
+    for n, m in net.named_modules():  # 1x1 conv shapes for the report
+        if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (1, 1) and m.groups == 1:
+            shapes[n] = [m.in_channels, m.out_channels]
+    os.makedirs(os.path.dirname(os.path.abspath(args.markers)), exist_ok=True)
+    with open(args.markers, 'w') as f:
+        json.dump(dict(order=order, conv1x1=shapes, batch=args.batch, res=args.res,
+                       feature_shape=list(feat.shape)), f)
+    print(f'recorded {len(order)} markers')
+
+
+def _kernels(trace_dir):
+    paths = glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True)
+    if not paths:
+        raise SystemExit(f'no *kernel_trace.csv under {trace_dir}')
+    rows = []
+    for p in paths:
+        with open(p) as f:
+            for r in csv.DictReader(f):
+                rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name']))
+    rows.sort()
+    return rows
+
+
+def _kind(kname):
+    k = kname.lower()
+    if MARK in k:
+        return 'marker'
+    if 'se_gate' in k:
+        return 'se_gate'
+    if 'bias_act' in k:
+        return 'K10'
+    if 'depthwise' in k:
+        return 'K11'
+    if k.startswith('cijk') or 'gemm' in k:
+        return 'gemm'
+    if 'sigmoid' in k:
+        return 'sigmoid'
+    if 'silu' in k:
+        return 'silu'
+    if 'mul' in k or 'binaryfunctor' in k:
+        return 'binary'
+    if 'miopen' in k or 'conv' in k:
+        return 'conv'
+    return 'other'
+
+
+def _role(module, kind):
+    """Role of a kernel inside its MBConv block from the module that launched it and its kind."""
+    parts = module.split('.')
+    last = parts[-1]
+    if kind in ('K10', 'K11', 'se_gate'):
+        return kind
+    if last == 'fc1':
+        return 'SE fc1' if kind == 'gemm' else 'SE fc1 bias'
+    if last == 'fc2':
+        return 'SE fc2' if kind == 'gemm' else 'SE fc2 bias'
+    if last == 'act':
+        return 'SE act'
+    if last == 'gate':
+        return 'SE gate fn' if kind == 'sigmoid' else 'x * gate'
+    if kind == 'binary':
+        return 'x * gate'
+    return None
+
+
+def report(args):
+    meta = json.load(open(args.markers))
+    order = meta['order']
+    rows = _kernels(args.trace)
+    marks = [i for i, r in enumerate(rows) if MARK in r[2]]
+    # the marked forward is the last run of len(order) consecutive markers
+    if len(marks) < len(order):
+        raise SystemExit(f'{len(marks)} markers in the trace, {len(order)} recorded')
+    marks = marks[-len(order):]
+    per_kernel = []   # (module, kind, kernel name, us)
+    for j, mi in enumerate(marks):
+        end = marks[j + 1] if j + 1 < len(marks) else len(rows)
+        for r in rows[mi + 1:end]:
+            per_kernel.append((order[j], _kind(r[2]), r[2], (r[1] - r[0]) / 1e3))
+    total = sum(k[3] for k in per_kernel)
+    pat = re.compile(r'^1\.(\d+)\.(\d+)\.block\.(\d+)')
+    blocks = OrderedDict()
+    proj = defaultdict(list)
+    convs = meta['conv1x1']
+    for module, kind, kname, us in per_kernel:
+        m = pat.match(module)
+        if not m:
+            continue
+        stage, idx, layer = int(m.group(1)), int(m.group(2)), int(m.group(3))
+        if stage < 4:
+            continue  # FusedMBConv stages: no squeeze-excite
+        key = (stage, idx)
+        b = blocks.setdefault(key, defaultdict(float))
+        role = _role(module, kind)
+        if role == 'K10' and layer != 3:
+            role = None  # the expand layer's epilogue: not part of the tail
+        if role is None:
+            # the MBConv layers: '0' expand 1x1, '1' depthwise, '2' SE, '3' project
+            role = {0: 'expand', 1: 'depthwise', 2: 'SE other', 3: 'project'}.get(layer, f'layer {layer}')
+            if role == 'project' and kind in ('gemm', 'conv'):
+                proj[tuple(convs.get(module, ('?',)))].append(us)
+            role = role if kind in ('gemm', 'conv', 'K11') else f'{role} {kind}'
+        b[role] += us
+    tail_roles = ['SE fc1', 'SE fc1 bias', 'SE act', 'SE fc2', 'SE fc2 bias', 'SE gate fn', 'se_gate', 'x * gate',
+                  'project', 'K10']
+    roles = [r for r in tail_roles if any(r in b for b in blocks.values())]
+    others = sorted({r for b in blocks.values() for r in b} - set(roles))
+    lines = [f'# Backbone per-layer kernel times: EfficientNetV2-S, batch {meta["batch"]}, {meta["res"]} px, f32',
+             '', f'{args.title}', '',
+             f'One marked forward (tools/backbone_trace.py): {len(per_kernel)} kernels, {total:.1f} us of kernel '
+             f'time (markers excluded).  Times in us.  "tail" = the squeeze-excite roles + x * gate + project + '
+             f'K10 (where a kernel is attributed to "K11" it is the depthwise layer, not the tail).', '',
+             '| stage.block | ' + ' | '.join(roles) + ' | **tail** | ' + ' | '.join(others) + ' |',
+             '|---|' + '---|' * (len(roles) + 1 + len(others))]
+    sums = defaultdict(float)
+    for (stage, idx), b in blocks.items():
+        tail = sum(b.get(r, 0.0) for r in roles)
+        for r in roles + others:
+            sums[r] += b.get(r, 0.0)
+        sums['tail'] += tail
+        lines.append(f'| {stage}.{idx} | ' + ' | '.join(f'{b.get(r, 0.0):.1f}' for r in roles)
+                     + f' | **{tail:.1f}** | ' + ' | '.join(f'{b.get(r, 0.0):.1f}' for r in others) + ' |')
+    lines.append('| **sum** | ' + ' | '.join(f'{sums[r]:.1f}' for r in roles) + f' | **{sums["tail"]:.1f}** | '
+                 + ' | '.join(f'{sums[r]:.1f}' for r in others) + ' |')
+    se_chain = sum(sums[r] for r in roles if r.startswith('SE') or r in ('se_gate', 'x * gate'))
+    lines += ['', f'Squeeze-excite chain incl. x * gate, stages 4-6: **{se_chain:.1f} us**; '
+                  f'whole tail: **{sums["tail"]:.1f} us**; whole forward: {total:.1f} us.', '',
+              '## Project GEMMs by shape (Cin -> Cout)', '', '| Cin -> Cout | calls | avg us | sum us |', '|---|---|---|---|']
+    for shape, v in sorted(proj.items()):
+        lines.append(f'| {" -> ".join(map(str, shape))} | {len(v)} | {sum(v) / len(v):.1f} | {sum(v):.1f} |')
+    kinds = defaultdict(float)
+    for _, kind, _, us in per_kernel:
+        kinds[kind] += us
+    lines += ['', '## Whole forward by kernel kind', '', '| kind | us |', '|---|---|']
+    lines += [f'| {k} | {v:.1f} |' for k, v in sorted(kinds.items(), key=lambda kv: -kv[1])]
+    with open(args.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+    print('\n'.join(lines[:8] + lines[-30:]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest='cmd', required=True)
+    r = sub.add_parser('record')
+    r.add_argument('--markers', required=True)
+    r.add_argument('--batch', type=int, default=64)
+    r.add_argument('--res', type=int, default=256)
+    r.add_argument('--warmup', type=int, default=3)
+    p = sub.add_parser('report')
+    p.add_argument('--trace', required=True)
+    p.add_argument('--markers', required=True)
+    p.add_argument('--out', required=True)
+    p.add_argument('--title', default='')
+    args = ap.parse_args()
+    (record if args.cmd == 'record' else report)(args)
+
+
+if __name__ == '__main__':
+    main()
