@@ -506,6 +506,18 @@ int mtr_se_gate(const float* mean /*[B*C]*/, const float* w1, const float* b1, c
                 const float* b2, int act, int gate_fn, int B, int C, int S, float* gate /*[B*C]*/,
                 mtr_stream_t stream);
 
+/* K13 (outside the reference's hot path, like K10): a 1x1 stride-1 unpadded convolution of the backbone's
+ * inference copy as one f32 MFMA GEMM with the K10 epilogue and the squeeze-excite gate folded in:
+ *   y[b, m, p] = act(bias[m] + sum_k weight[m, k] * (x[b, k, p] * gate[b, k])) (+ residual[b, m, p])
+ * x [B, K, HW], y and residual [B, M, HW] (NCHW, contiguous, 16-byte aligned), weight [M, K] row-major
+ * (the folded conv weight, 16-byte aligned), bias [M]; gate [B, K] and residual may be NULL.  The sum is
+ * an f32 fmaf chain in k order 0, 1, 2, ...; act: as mtr_bias_act_nchw, the residual added after it.
+ * f32 only (else MTR_E_DTYPE); HW and K multiples of 4 (else MTR_E_SHAPE: the caller takes the
+ * library-GEMM path); y must not alias x.  No atomics: the same inputs give the same bits. */
+int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weight, const float* bias,
+                         const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
+                         int M, int K, int HW, void* y, mtr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,9 @@ class SqueezeExcite(nn.Module):
     # set by fold_batchnorm(fused_epilogue=True): the ConvBiasAct in front of this block, whose
     # epilogue pass also produced the per-channel mean of the tensor it handed over
     mean_from = ()
+    # set by fold_batchnorm(fused_epilogue=True): the ConvBiasAct of the block's project conv, which
+    # applies the gate to its input itself when it runs on K13
+    gate_to = ()
 
     _GATE_NAMES = {nn.Sigmoid: 'sigmoid', nn.Hardsigmoid: 'hardsigmoid'}
 
@@ -81,6 +84,11 @@ class SqueezeExcite(nn.Module):
             from . import kernels
             g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
                                 _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)])
+            for dst in self.gate_to:
+                if dst.k13_takes(x):
+                    # the project conv (K13) multiplies x by the gate as it stages x: no x * g pass
+                    dst.give_gate(x, g)
+                    return x
             return x * g.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         s = None if mean is None else mean.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         if s is None:
@@ -284,6 +292,33 @@ class ConvBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
+        self._gate = None
+        self.last_path = None  # 'k13', 'k13_gate' or 'library': what the last forward ran (tests, A/B runs)
+
+    # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
+    use_k13 = True
+    # (Cin, Cout, H * W) where K13 measured slower than rocBLAS + K10 (+ x * gate) at the bench shape
+    # (EfficientNetV2-S, batch 64, 256 px): these stay on the library path
+    k13_slower = frozenset({(960, 256, 64), (1536, 256, 64), (256, 1280, 64)})
+
+    def k13_takes(self, x):
+        """Whether forward(x) runs on K13 (conv1x1.hip): a 1x1 stride-1 unpadded ungrouped conv on an f32
+        CUDA NCHW-contiguous input, autocast off, no gradient wanted, a shape the C entry accepts."""
+        c = self.conv
+        if not (ConvBiasAct.use_k13 and not self.emit_mean and x.is_cuda and c.kernel_size == (1, 1)
+                and c.stride == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1
+                and c.bias is None and c.padding_mode == 'zeros'):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
+            return False
+        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k13_slower:
+            return False
+        from . import kernels
+        return kernels.conv1x1_supported(x, c.weight)
+
+    def give_gate(self, x, gate):
+        """Hands over the squeeze-excite gate [B, C] f32 of `x`: the next forward(x) applies it."""
+        self._gate = (x, gate)
 
     def take_mean_f32(self, x):
         """The [B, C] f32 mean of `x` if `x` is the very tensor this module returned last."""
@@ -298,6 +333,17 @@ class ConvBiasAct(nn.Module):
         return None if m is None else m.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
 
     def forward(self, x, residual=None):
+        held, self._gate = self._gate, None
+        gate = held[1] if held is not None and held[0] is x else None
+        if self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                                       and residual.data_ptr() % 16 == 0)):
+            from . import kernels
+            self.last_path = 'k13' if gate is None else 'k13_gate'
+            return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, gate=gate,
+                                            residual=residual)
+        self.last_path = 'library'
+        if gate is not None:  # (not reached when the gate was handed over: k13_takes(x) was checked)
+            x = x * gate.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         y = self.conv(x)
         # K10 moves 16 bytes per lane: planes of a multiple of the vector width (7x7 maps at 224 px,
         # 5x5 at 160 px are not), 16-byte aligned storage; everything else takes the torch ops
@@ -434,6 +480,15 @@ def fold_batchnorm(backbone, fused_epilogue=False):
                         all(isinstance(m, nn.Identity) for m in list(prev)[1:]):
                     prev[0].emit_mean = True
                     nxt.mean_from = (prev[0],)
+        # squeeze-excite -> project conv: the gate multiplies the project conv's input inside K13
+        for seq in folded.modules():
+            if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
+                continue
+            kids = list(seq)
+            for prev, nxt in zip(kids, kids[1:]):
+                if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and \
+                        isinstance(nxt[0], ConvBiasAct):
+                    prev.gate_to = (nxt[0],)
     return folded
 
 

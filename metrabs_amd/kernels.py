@@ -648,3 +648,43 @@ def se_gate(mean, w1, b1, w2, b2, act, gate_fn, out=None):
     check(_lib.load().mtr_se_gate(*(_ptr(t) for t in tensors), ACT_CODES[act], SE_GATE_CODES[gate_fn], B, C, S,
                                   _ptr(out), current_stream_ptr(mean.device)), 'mtr_se_gate')
     return out
+
+
+# K13: 1x1 convolution as one f32 MFMA GEMM with the K10 epilogue (csrc/conv1x1.hip)
+
+def conv1x1_supported(x, weight):
+    """Whether mtr_conv1x1_bias_act takes this input: f32, NCHW-contiguous, 16-byte aligned, H*W and
+    Cin multiples of 4 (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a call)."""
+    if x.dim() != 4 or x.dtype != torch.float32 or weight.dtype != torch.float32 or not x.is_contiguous():
+        return False
+    K, HW = x.shape[1], x.shape[2] * x.shape[3]
+    return (weight.numel() == weight.shape[0] * K and HW % 4 == 0 and K % 4 == 0
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+            and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
+
+
+def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None):
+    """y = act(conv1x1(x * gate[:, :, None, None], w) + bias) (+ residual) in one launch on the current
+    stream: x [B, K, H, W] f32 NCHW-contiguous, w [M, K] (or the [M, K, 1, 1] conv weight), bias [M],
+    gate [B, K] f32 or None, residual [B, M, H, W] or None.  Stride 1, no padding; an f32 MFMA GEMM
+    in a fixed k order (the same bits on every call and graph replay)."""
+    require_cuda(x, w, bias, gate, residual)
+    B, K, H, W = x.shape
+    M = w.shape[0]
+    w = w.reshape(M, -1)
+    if w.shape[1] != K:
+        raise ValueError(f'conv1x1_bias_act: weight has {w.shape[1]} input channels, x has {K}')
+    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != B * K):
+        raise ValueError('conv1x1_bias_act: gate must be [B, Cin] f32')
+    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
+                                 or not residual.is_contiguous()):
+        raise ValueError('conv1x1_bias_act: residual must be [B, Cout, H, W] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('conv1x1_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
+    check(_lib.load().mtr_conv1x1_bias_act(
+        _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
+        None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act')
+    return out

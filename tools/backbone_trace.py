@@ -91,6 +91,8 @@ def _kind(kname):
         return 'marker'
     if 'se_gate' in k:
         return 'se_gate'
+    if 'conv1x1_kernel' in k:  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
+        return 'K13'
     if 'bias_act' in k:
         return 'K10'
     if 'depthwise' in k:
@@ -161,9 +163,10 @@ def report(args):
         if role is None:
             # the MBConv layers: '0' expand 1x1, '1' depthwise, '2' SE, '3' project
             role = {0: 'expand', 1: 'depthwise', 2: 'SE other', 3: 'project'}.get(layer, f'layer {layer}')
-            if role == 'project' and kind in ('gemm', 'conv'):
-                proj[tuple(convs.get(module, ('?',)))].append(us)
-            role = role if kind in ('gemm', 'conv', 'K11') else f'{role} {kind}'
+            if role == 'project' and kind in ('gemm', 'conv', 'K13'):
+                # (K13 runs inside the ConvBiasAct, the library GEMM inside its .conv)
+                proj[tuple(convs.get(module) or convs.get(module + '.conv', ('?',)))].append(us)
+            role = role if kind in ('gemm', 'conv', 'K11', 'K13') else f'{role} {kind}'
         b[role] += us
     tail_roles = ['SE fc1', 'SE fc1 bias', 'SE act', 'SE fc2', 'SE fc2 bias', 'SE gate fn', 'se_gate', 'x * gate',
                   'project', 'K10']
