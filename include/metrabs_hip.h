@@ -518,6 +518,20 @@ int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weight, const fl
                          const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
                          int M, int K, int HW, void* y, mtr_stream_t stream);
 
+/* K13h (outside the reference's hot path, like K10): mtr_conv1x1_bias_act for f16 / bf16 tensors, one 16-bit
+ * MFMA GEMM (v_mfma_f32_32x32x16_{f16,bf16}) with the K10 epilogue and the squeeze-excite gate folded in:
+ *   xg[b, k, p] = x[b, k, p], or rnd16(x[b, k, p] * rnd16(gate[b, k])) with a gate (torch's x * gate.to(x.dtype))
+ *   y[b, m, p]  = rnd16(act(bias[m] + sum_k weight[m, k] * xg[b, k, p]) (+ residual[b, m, p]))
+ * x [B, K, HW], y and residual [B, M, HW] (NCHW, contiguous, 16-byte aligned), weight [M, K] row-major, all in
+ * `dtype` (MTR_F16 or MTR_BF16, else MTR_E_DTYPE); bias [M] and gate [B, K] f32 (4-byte aligned); gate and
+ * residual may be NULL.  The sum is accumulated in f32 in 16-k MFMA steps in k order, the epilogue is f32 in
+ * K10's order (act, then the residual), rounded to 16 bits once (to nearest even).  HW and K multiples of 8
+ * (else MTR_E_SHAPE: the caller takes the library-GEMM path); y must not alias x.  No atomics, no split-K:
+ * the same inputs give the same bits, whichever tile the shape picks. */
+int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weight, const float* bias,
+                           const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
+                           int M, int K, int HW, void* y, mtr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,8 @@ SIGNATURES = {
                             c_int, c_void_p, c_void_p]),
     'mtr_conv1x1_bias_act': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_conv1x1_bias_act16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -85,15 +85,24 @@ class SqueezeExcite(nn.Module):
             g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
                                 _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)])
             for dst in self.gate_to:
-                if dst.k13_takes(x):
-                    # the project conv (K13) multiplies x by the gate as it stages x: no x * g pass
+                if dst.k13_takes(x) or dst.k13h_takes(x):
+                    # the project conv (K13 / K13h) multiplies x by the gate as it stages x: no x * g pass
                     dst.give_gate(x, g)
                     return x
             return x * g.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
+        if x.dtype != self.fc1.weight.dtype and not torch.is_autocast_enabled(x.device.type):
+            return self._forward_16bit_copy(x, mean)
         s = None if mean is None else mean.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         if s is None:
             s = x.mean((2, 3), keepdim=True)
         return x * self.gate(self.fc2(self.act(self.fc1(s))))
+
+    def _forward_16bit_copy(self, x, mean):
+        """The unfused block in a 16-bit copy (fold_batchnorm(dtype=)): its parameters stay f32, so does its
+        arithmetic, from the f32 mean (the epilogue's, or one taken here); x * gate in x's dtype."""
+        s = mean.view(x.shape[0], x.shape[1], 1, 1) if mean is not None else \
+            x.mean((2, 3), keepdim=True, dtype=self.fc1.weight.dtype)
+        return x * self.gate(self.fc2(self.act(self.fc1(s)))).to(x.dtype)
 
     def _fused_gate_ok(self):
         """K12 computes no gradient: only where none is wanted, for the layer types it implements."""
@@ -293,7 +302,8 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        self.last_path = None  # 'k13', 'k13_gate' or 'library': what the last forward ran (tests, A/B runs)
+        # 'k13', 'k13_gate', 'k13h', 'k13h_gate' or 'library': what the last forward ran (tests, A/B runs)
+        self.last_path = None
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
     use_k13 = True
@@ -316,6 +326,33 @@ class ConvBiasAct(nn.Module):
         from . import kernels
         return kernels.conv1x1_supported(x, c.weight)
 
+    # class-wide switch (tests and A/B runs): 1x1 convolutions of a 16-bit copy on K13h instead of
+    # rocBLAS + K10 (+ x * gate)
+    use_k13h = True
+    # (Cin, Cout, H * W) where K13h measured slower than that library path (unpinned, as the copy runs) in f16 or
+    # bf16, both timed as HIP graph replays (EfficientNetV2-S batch 64 at 256 px, EfficientNetV2-L batch 32 at
+    # 384 px; DESIGN.md section 12, profiles/r09a_conv1x1_ab_*.jsonl)
+    k13h_slower = frozenset({(192, 48, 4096), (256, 64, 1024), (1536, 256, 64), (256, 64, 9216), (768, 192, 576),
+                             (1152, 224, 576), (1344, 224, 576), (1344, 384, 144), (2304, 384, 144),
+                             (2304, 640, 144), (640, 3840, 144), (3840, 640, 144), (640, 1280, 144)})
+
+    def k13h_takes(self, x):
+        """Whether forward(x) runs on K13h (conv1x1_16.hip): a 1x1 stride-1 unpadded ungrouped conv of a 16-bit
+        copy (fold_batchnorm(dtype=)) on a CUDA NCHW-contiguous input of the copy's dtype, autocast off, no
+        gradient wanted, a shape the C entry accepts."""
+        c = self.conv
+        if not (ConvBiasAct.use_k13h and not self.emit_mean and x.is_cuda and x.dtype == c.weight.dtype
+                and x.dtype in (torch.float16, torch.bfloat16) and c.kernel_size == (1, 1)
+                and c.stride == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1
+                and c.bias is None and c.padding_mode == 'zeros'):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
+            return False
+        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k13h_slower:
+            return False
+        from . import kernels
+        return kernels.conv1x1_16_supported(x, c.weight)
+
     def give_gate(self, x, gate):
         """Hands over the squeeze-excite gate [B, C] f32 of `x`: the next forward(x) applies it."""
         self._gate = (x, gate)
@@ -335,6 +372,15 @@ class ConvBiasAct(nn.Module):
     def forward(self, x, residual=None):
         held, self._gate = self._gate, None
         gate = held[1] if held is not None and held[0] is x else None
+        w16 = self.conv.weight.dtype
+        if x.dtype != w16 and w16 in (torch.float16, torch.bfloat16) and not torch.is_autocast_enabled(x.device.type):
+            x = x.to(w16)  # the first convolution of a 16-bit copy: the input is cast once, here
+        if self.k13h_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                                        and residual.data_ptr() % 16 == 0)):
+            from . import kernels
+            self.last_path = 'k13h' if gate is None else 'k13h_gate'
+            return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
+                                              residual=residual)
         if self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
                                                        and residual.data_ptr() % 16 == 0)):
             from . import kernels
@@ -427,7 +473,7 @@ def _block_plus_skip(block, x):
     return x + block(x)
 
 
-def fold_batchnorm(backbone, fused_epilogue=False):
+def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -435,11 +481,20 @@ def fold_batchnorm(backbone, fused_epilogue=False):
     11.6 -> 10.2 ms under f16 autocast (tools/experiments/bn_backend_probe.py).  The original keeps
     its checkpoint-compatible parameters; the copy has conv biases and no BatchNorm2d.
     fused_epilogue=True additionally runs "+ bias, activation" behind each folded convolution as one
-    in-place HIP pass (ConvBiasAct) instead of PyTorch-ROCm's two elementwise kernels."""
+    in-place HIP pass (ConvBiasAct) instead of PyTorch-ROCm's two elementwise kernels.
+    dtype=torch.float16 / torch.bfloat16 (needs fused_epilogue=True) returns a 16-bit inference copy: the batch
+    norms are folded in f32, then every convolution weight that runs as a GEMM or MIOpen convolution (1x1, dense
+    3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise layers (K11) and the
+    squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast at the first
+    convolution; run it with autocast off) and its 1x1 stride-1 convolutions run on K13h."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
         raise ValueError('fold_batchnorm needs the running statistics of an eval-mode network')
+    if dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError(f'fold_batchnorm: dtype must be None, torch.float16 or torch.bfloat16, got {dtype}')
+    if dtype is not None and not fused_epilogue:
+        raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -489,6 +544,11 @@ def fold_batchnorm(backbone, fused_epilogue=False):
                 if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and \
                         isinstance(nxt[0], ConvBiasAct):
                     prev.gate_to = (nxt[0],)
+    if dtype is not None:  # the 16-bit copy: GEMM / MIOpen weights cast once, not by autocast on every forward
+        for m in folded.modules():
+            if isinstance(m, ConvBiasAct):
+                m.conv.to(dtype)
+        folded.inference_dtype = dtype
     return folded
 
 

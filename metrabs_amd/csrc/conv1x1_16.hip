@@ -1,0 +1,292 @@
+// K13h: K13 (conv1x1.hip) for f16 / bf16 tensors -- a 1x1 stride-1 NCHW convolution as one 16-bit MFMA
+// GEMM with the K10 epilogue and the squeeze-excite gate folded in.
+//
+// Not part of the reference's hot path (like K10 - K13): the expand and project convolutions of the
+// backbone's 16-bit inference copy (backbones.fold_batchnorm(fused_epilogue=True, dtype=f16 / bf16)).
+// PyTorch-ROCm runs each as a rocBLAS 16-bit GEMM, then K10, and the project conv behind a separate
+// "x * gate" pass.  Here, per image b, in one launch:
+//
+//   xg[b, k, p] = x[b, k, p]                                    (no gate)
+//               = rnd16(f32(x[b, k, p]) * f32(rnd16(gate[b, k])))  (torch's x * gate.to(x.dtype), bit for bit)
+//   y[b, m, p]  = rnd16(act(bias[m] + sum_k W[m, k] * xg[b, k, p]) (+ residual[b, m, p]))
+//
+// accumulated in f32, the epilogue in f32 in K10's order, rounded to 16 bits once (round to nearest even,
+// plain casts).  The GEMM is computed transposed, Y_b^T = X_b^T W^T, on v_mfma_f32_32x32x16_{f16,bf16}:
+// the A operand is a 32 (positions) x 16 (k) slice of X^T, the B operand a 16 (k) x 32 (channels) slice of
+// W^T.  Lane (r, h) = (lane & 31, lane >> 5) holds A[r][8h .. 8h+7] and B[8h .. 8h+7][r]: eight CONSECUTIVE
+// k of one position and of one weight row.  W is row-major [M][K], so its fragment is one 16-byte load
+// straight from global memory (L2-resident; each wave owns its rows, nothing to share through LDS).  X is
+// k-strided (NCHW): a k-tile is staged global -> registers -> LDS as an X^T image ([position][k], rows
+// padded so that the 16-byte fragment reads of 16 consecutive positions hit distinct banks), transposed on
+// the way in -- each loader thread reads 4 k-rows x 8 positions (four 16-byte loads) and writes 8 positions
+// x 4 k (eight 8-byte LDS writes).  Every lane of the accumulator holds four consecutive positions of one
+// output channel: one 8-byte store per group, the epilogue applied in registers on the way out.
+//
+// The column index runs over (image, position) jointly like K13's; HW % 8 == 0, so a loader group of 8
+// positions never straddles two images.  Two LDS buffers (the next tile's loads are in flight while the
+// current one is multiplied); rows past M, columns past B * HW and k past K are zero-filled, never stored.
+// The k order is the same in every configuration -- 16-k MFMA steps at 0, 16, 32, ... -- so the result
+// does not depend on the tile picked.  No atomics, no split-K: the same inputs give the same bits.
+#include "common.h"
+
+namespace mtr {
+
+typedef float c16_f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+template <int DT> struct Bits16;
+template <> struct Bits16<MTR_F16> {
+  typedef _Float16 v8 __attribute__((ext_vector_type(8)));
+  static __device__ __forceinline__ float f32(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
+  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+  static __device__ __forceinline__ c16_f32x16 mfma(uint4 a, uint4 b, c16_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
+  }
+};
+template <> struct Bits16<MTR_BF16> {
+  typedef __bf16 v8 __attribute__((ext_vector_type(8)));
+  static __device__ __forceinline__ float f32(unsigned short b) { return (float)__builtin_bit_cast(__bf16, b); }
+  // a plain cast: v_cvt_pk_bf16_f32, round to nearest even, a NaN stays a NaN
+  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+  static __device__ __forceinline__ c16_f32x16 mfma(uint4 a, uint4 b, c16_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
+  }
+};
+
+template <int V> struct ActTag { static constexpr int value = V; };
+
+constexpr int kC16Pad = 8;  // X^T image row pad (16-bit elements): rows (BK + 8) * 2 bytes apart
+
+// WM x WN waves, each FM x FN tiles of 32 x 32 (channels x positions), k-tiles of BK
+template <int DT, int WM, int WN, int FM, int FN, int BK>
+__global__ __launch_bounds__(64 * WM * WN) void conv1x1_16_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ gate, const unsigned short* __restrict__ residual, unsigned short* __restrict__ y,
+    int M, int K, int HW, int n_total, FastDiv by_hw, int act) {
+  using H = Bits16<DT>;
+  constexpr int NT = 64 * WM * WN;
+  constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
+  constexpr int LDK = BK + kC16Pad;           // elements per X^T image row (one position)
+  constexpr int KS = BK / 16;                 // MFMA k-steps per tile
+  constexpr int UNITS = (BK / 4) * (BN / 8);  // loader units of 4 k x 8 positions
+  static_assert(BK % 16 == 0 && UNITS <= NT, "one loader unit per thread at most");
+  __shared__ __attribute__((aligned(16))) unsigned short xs[2][BN * LDK];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave % WM, wn = wave / WM;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const int r = lane & 31, h = lane >> 5;
+
+  // this thread's loader unit: positions 8 p8 .. 8 p8 + 7 of the tile, k 4 k4 .. 4 k4 + 3 of each k-tile
+  const int p8 = tid % (BN / 8), k4 = tid / (BN / 8);
+  const int xcol = n0 + 8 * p8;
+  const bool xload = tid < UNITS && xcol < n_total;
+  const unsigned xb = xload ? fastdiv((unsigned)xcol, by_hw) : 0u;
+  const unsigned short* xsrc = x + (long long)xb * K * HW + (xcol - (int)xb * HW);
+  const float* gsrc = gate ? gate + (long long)xb * K : nullptr;
+
+  // the next tile's x rows and gate values: loaded in load_x, first used in store_x (behind this tile's
+  // MFMAs), so the loads stay in flight while the current tile is multiplied
+  u16x8 xr[4];
+  float gr[4];
+  auto load_x = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = k0 + 4 * k4 + i;
+      u16x8 t = (u16x8)0;
+      float g = 0.0f;
+      if (xload && k < K) {
+        t = __builtin_bit_cast(u16x8, *reinterpret_cast<const uint4*>(xsrc + (long long)k * HW));
+        if (gsrc) g = gsrc[k];
+      }
+      xr[i] = t;
+      gr[i] = g;
+    }
+  };
+  auto store_x = [&](int buf) {  // 4 k-rows x 8 positions -> 8 positions x 4 k of the X^T image
+    if (tid < UNITS) {
+      if (gsrc) {  // the squeeze-excite gate, once per staged element, rounded as torch's x * gate.to(x.dtype)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float g = H::f32(H::rnd(gr[i]));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xr[i][e] = H::rnd(H::f32(xr[i][e]) * g);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        uint2 v;
+        v.x = (unsigned)xr[0][j] | ((unsigned)xr[1][j] << 16);
+        v.y = (unsigned)xr[2][j] | ((unsigned)xr[3][j] << 16);
+        *reinterpret_cast<uint2*>(&xs[buf][(8 * p8 + j) * LDK + 4 * k4]) = v;
+      }
+    }
+  };
+  // this lane's weight fragments: rows m0 + wm * 32 FM + 32 i + r, k 16 s + 8 h .. + 7 of each k-tile
+  auto load_w = [&](uint4 (&wr)[FM][KS], int k0) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const int m = m0 + wm * (32 * FM) + 32 * i + r;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const int k = k0 + 16 * s + 8 * h;
+        uint4 t = make_uint4(0u, 0u, 0u, 0u);
+        if (m < M && k < K) t = *reinterpret_cast<const uint4*>(w + (long long)m * K + k);
+        wr[i][s] = t;
+      }
+    }
+  };
+
+  c16_f32x16 acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+
+  uint4 wc[FM][KS], wnx[FM][KS];
+  const int n_tiles = (K + BK - 1) / BK;
+  load_x(0);
+  load_w(wc, 0);
+  store_x(0);
+  __syncthreads();
+  for (int t = 0; t < n_tiles; ++t) {
+    const int buf = t & 1;
+    if (t + 1 < n_tiles) {  // in flight during this tile's MFMAs
+      load_x((t + 1) * BK);
+      load_w(wnx, (t + 1) * BK);
+    }
+    const unsigned short* xa = &xs[buf][(wn * (32 * FN) + r) * LDK + 8 * h];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      uint4 a[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) a[j] = *reinterpret_cast<const uint4*>(xa + (32 * j) * LDK + 16 * s);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = H::mfma(a[j], wc[i][s], acc[i][j]);
+    }
+    if (t + 1 < n_tiles) {
+      store_x(buf ^ 1);  // the other buffer: last read before the previous barrier
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) wc[i][s] = wnx[i][s];
+    }
+    __syncthreads();
+  }
+
+  // epilogue: lane holds channel m = .. + r, positions 8 g + 4 h + 0..3 of each 32-column tile
+  auto epilogue = [&](auto tag) {
+    constexpr int ACT = decltype(tag)::value;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const int m = m0 + wm * (32 * FM) + 32 * i + r;
+      if (m >= M) continue;
+      const float bm = bias[m];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int col = n0 + wn * (32 * FN) + 32 * j + 8 * g + 4 * h;
+          if (col >= n_total) continue;
+          const unsigned b = fastdiv((unsigned)col, by_hw);
+          const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = activate<ACT>(acc[i][j][4 * g + e] + bm);
+          if (residual) {  // the block's skip connection, added after the activation (K10's order)
+            const uint2 q = *reinterpret_cast<const uint2*>(residual + off);
+            v[0] += H::f32((unsigned short)(q.x & 0xffffu));
+            v[1] += H::f32((unsigned short)(q.x >> 16));
+            v[2] += H::f32((unsigned short)(q.y & 0xffffu));
+            v[3] += H::f32((unsigned short)(q.y >> 16));
+          }
+          uint2 o;
+          o.x = (unsigned)H::rnd(v[0]) | ((unsigned)H::rnd(v[1]) << 16);
+          o.y = (unsigned)H::rnd(v[2]) | ((unsigned)H::rnd(v[3]) << 16);
+          *reinterpret_cast<uint2*>(y + off) = o;
+        }
+      }
+    }
+  };
+  switch (act) {  // wave-uniform: one epilogue body per activation, the GEMM shared
+    case kActRelu: epilogue(ActTag<kActRelu>()); break;
+    case kActSilu: epilogue(ActTag<kActSilu>()); break;
+    case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
+    default: epilogue(ActTag<kActNone>()); break;
+  }
+}
+
+// The tile table, chosen from the shape only:
+//   tall  (WM w, WN 1, FM 1, FN 1, BK 64): 32 w x 32, w = ceil(M / 32) <= 5 -- few output channels (the
+//          project convs): the whole of M in one workgroup, every position read once
+//   tall4 at M = 256, K >= 512 (8x8 projects): two workgroups of 4 waves per 32 columns
+//   square(WM 2, WN 2, FM 2, FN 2, BK 32): 128 x 128 -- many output channels (expand, head)
+enum Conv1x1Config16 { kCfg16Tall = 0, kCfg16Square = 1 };
+
+struct Conv1x1Plan16 { int cfg, waves_m; };
+
+inline Conv1x1Plan16 pick_config16(int M, int K) {
+  if (M <= 160) return {kCfg16Tall, (M + 31) / 32};
+  if (M == 256 && K >= 512) return {kCfg16Tall, 4};
+  return {kCfg16Square, 2};
+}
+
+template <int DT, int WM, int WN, int FM, int FN, int BK>
+static int launch_conv1x1_16_cfg(const void* x, const void* w, const float* bias, const float* gate,
+                                 const void* residual, void* y, int act, int M, int K, int HW, long long n_total,
+                                 hipStream_t stream) {
+  constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
+  const long long gx = (n_total + BN - 1) / BN, gy = (M + BM - 1) / BM;
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WM * WN);
+  const FastDiv by_hw = make_fastdiv((unsigned)HW);
+  MTR_CLEAR_STALE();
+  hipLaunchKernelGGL((conv1x1_16_kernel<DT, WM, WN, FM, FN, BK>), grid, block, 0, stream,
+                     (const unsigned short*)x, (const unsigned short*)w, bias, gate, (const unsigned short*)residual,
+                     (unsigned short*)y, M, K, HW, (int)n_total, by_hw, act);
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
+template <int DT>
+static int launch_conv1x1_16(const void* x, const void* w, const float* bias, const float* gate, const void* residual,
+                             void* y, int act, int M, int K, int HW, long long n_total, hipStream_t s) {
+  const Conv1x1Plan16 p = pick_config16(M, K);
+  if (p.cfg == kCfg16Square)
+    return launch_conv1x1_16_cfg<DT, 2, 2, 2, 2, 32>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+  switch (p.waves_m) {
+    case 1: return launch_conv1x1_16_cfg<DT, 1, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    case 2: return launch_conv1x1_16_cfg<DT, 2, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    case 3: return launch_conv1x1_16_cfg<DT, 3, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    case 4: return launch_conv1x1_16_cfg<DT, 4, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    default: return launch_conv1x1_16_cfg<DT, 5, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+  }
+}
+
+}  // namespace mtr
+
+extern "C" int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weight, const float* bias,
+                                      const float* gate, const void* residual, int act, long long B, int M, int K,
+                                      int HW, void* y, mtr_stream_t stream) {
+  if (!x || !weight || !bias || !y) return MTR_E_NULL;
+  if (dtype != MTR_F16 && dtype != MTR_BF16) return MTR_E_DTYPE;
+  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
+  // 16-byte groups: eight positions of a k-row of x, eight k of a weight row
+  if (HW % 8 || K % 8) return MTR_E_SHAPE;
+  if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
+    return MTR_E_SHAPE;
+  if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
+  if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
+      ((uintptr_t)bias % 4) || ((uintptr_t)gate % 4))
+    return MTR_E_ALIGN;
+  if (x == y || (residual && residual == x)) return MTR_E_PARAM;  // y is written while x is still read
+  if (B == 0) return MTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MTR_F16)
+    return mtr::launch_conv1x1_16<MTR_F16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, s);
+  return mtr::launch_conv1x1_16<MTR_BF16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, s);
+}

@@ -688,3 +688,48 @@ def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None):
         None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
         ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act')
     return out
+
+
+# K13h: the same for f16 / bf16 tensors, one 16-bit MFMA GEMM (csrc/conv1x1_16.hip)
+
+def conv1x1_16_supported(x, weight):
+    """Whether mtr_conv1x1_bias_act16 takes this input: f16 or bf16 x and weight of one dtype, NCHW-contiguous,
+    16-byte aligned, H*W and Cin multiples of 8 (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked
+    without a call)."""
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or weight.dtype != x.dtype \
+            or not x.is_contiguous() or not weight.is_contiguous():
+        return False
+    K, HW = x.shape[1], x.shape[2] * x.shape[3]
+    return (weight.numel() == weight.shape[0] * K and HW % 8 == 0 and K % 8 == 0
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+            and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
+
+
+def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None):
+    """y = act(conv1x1(x * gate.to(x.dtype)[:, :, None, None], w) + bias) (+ residual) in one launch on the
+    current stream, for f16 / bf16: x [B, K, H, W] NCHW-contiguous, w [M, K] (or the [M, K, 1, 1] conv weight)
+    in x's dtype, bias [M] f32, gate [B, K] f32 or None, residual [B, M, H, W] in x's dtype or None.  Stride 1,
+    no padding; f32 accumulation in a fixed k order, rounded to x's dtype once (the same bits on every call
+    and graph replay)."""
+    require_cuda(x, w, bias, gate, residual)
+    B, K, H, W = x.shape
+    M = w.shape[0]
+    w = w.reshape(M, -1)
+    if w.shape[1] != K:
+        raise ValueError(f'conv1x1_bias_act16: weight has {w.shape[1]} input channels, x has {K}')
+    if w.dtype != x.dtype:
+        raise ValueError(f'conv1x1_bias_act16: weight is {w.dtype}, x is {x.dtype}')
+    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != B * K):
+        raise ValueError('conv1x1_bias_act16: gate must be [B, Cin] f32')
+    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
+                                 or not residual.is_contiguous()):
+        raise ValueError('conv1x1_bias_act16: residual must be [B, Cout, H, W] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('conv1x1_bias_act16: out must be [B, Cout, H, W] like the output, contiguous')
+    check(_lib.load().mtr_conv1x1_bias_act16(
+        _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
+        None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act16')
+    return out

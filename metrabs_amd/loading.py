@@ -54,13 +54,19 @@ def load_joint_info(model_dir):
     return JointInfo(ji['joint_names'], ji['joint_edges'])
 
 
-def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False):
+def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
     rounding, ~12 % less backbone time; fused_epilogue=True also runs bias + activation behind the
     folded convolutions as one in-place HIP pass, K10); the default keeps the checkpoint's own
-    arithmetic."""
+    arithmetic.  dtype=torch.float16 / torch.bfloat16 always gives the 16-bit folded copy with fused
+    epilogues (backbones.fold_batchnorm(dtype=)), whatever fold_batchnorm and fused_epilogue say."""
+    if dtype == torch.float32:
+        dtype = None
+    if dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError(f'load_crop_model: dtype must be None, torch.float32, torch.float16 or torch.bfloat16, '
+                         f'got {dtype}')
     cfg, raw = load_config(model_dir)
     # config.affine_weights (models/metrabs.py:23-32) is a path or a name under $DATA_ROOT/skeleton_conversion;
     # a file of that name shipped INSIDE the model directory is found too
@@ -76,16 +82,20 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     state = torch.load(os.path.join(model_dir, 'ckpt.pt'), map_location=map_location)
     model.load_state_dict(state, strict=True)
     model = model.eval()
-    if fold_batchnorm:
+    if dtype is not None:
+        from .backbones import fold_batchnorm as fold
+        model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype)
+    elif fold_batchnorm:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=fused_epilogue)
     return model
 
 
 def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchnorm=False,
-                           fused_epilogue=False):
-    """demo_image.py:49-56 -> Pose3dEstimator on `device`."""
-    model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue)
+                           fused_epilogue=False, dtype=None):
+    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype: as load_crop_model (a 16-bit copy also
+    makes the estimator sample 16-bit crops)."""
+    model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

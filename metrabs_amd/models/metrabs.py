@@ -324,11 +324,18 @@ class Metrabs(torch.nn.Module):
     # the parity target, where the pin costs 0.6 - 2.2 % of the step (EfficientNetV2-S; 5 % at EfficientNetV2-L) -- and not under 16-bit autocast, whose own
     # rounding (1.8 mm mean from the f32 model) is the size of the run-to-run noise and where the pin costs up
     # to 13 % (EfficientNetV2-L 384 f16: 1.86 k -> 1.62 k crops/s, profiles/r05z_bench_config4.json).
+    # A 16-bit backbone copy (backbones.fold_batchnorm(dtype=)) counts as 16-bit arithmetic like autocast: not pinned
+    # by default.
     deterministic_backbone = None
 
     def backbone_is_pinned(self):
         d = self.deterministic_backbone
-        return bool(self.autocast_dtype is None if d is None else d)
+        return bool(self.autocast_dtype is None and self.input_dtype == torch.float32 if d is None else d)
+
+    @property
+    def input_dtype(self):
+        """The dtype the backbone computes in and wants its crops in: a 16-bit copy's dtype, else f32."""
+        return getattr(self.backbone, 'inference_dtype', None) or torch.float32
 
     def _run_backbone(self, image):
         if self.backbone_is_pinned() and image.is_cuda:
@@ -358,7 +365,12 @@ class Metrabs(torch.nn.Module):
     def forward(self, inp, autocast_dtype=None):
         image, intrinsics = inp
         autocast_dtype = self.autocast_dtype if autocast_dtype is None else autocast_dtype
-        if autocast_dtype is not None:
+        in_dtype = self.input_dtype
+        if in_dtype != torch.float32:
+            # a 16-bit copy: its dtype IS its arithmetic (no autocast); an input of another dtype is cast once
+            with torch.autocast('cuda', enabled=False):
+                features = self._run_backbone(image.to(in_dtype))
+        elif autocast_dtype is not None:
             with torch.autocast('cuda', dtype=autocast_dtype):
                 features = self._run_backbone(image)
         else:

@@ -112,7 +112,8 @@ class Pose3dEstimator(torch.nn.Module):
             k: torch.tensor(v['edges'], dtype=torch.int32) for k, v in skeleton_infos.items()}
         self.skeleton_joint_indices_table = {k: v['indices'] for k, v in skeleton_infos.items()}
         self._tta_cache = {}
-        self.crop_dtype = torch.float32
+        # a crop model with a 16-bit backbone copy takes 16-bit crops: the sampler writes them directly
+        self.crop_dtype = getattr(crop_model, 'input_dtype', torch.float32)
         self.crop_channels_last = False
         self.shard_across_ranks = False
         self.force_collective = False   # run the final all-gather even in a process group of one rank

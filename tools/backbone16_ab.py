@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Whole-step A/B of the 16-bit backbone copy: bench.py's configs[1] (EfficientNetV2-S, 256 px, 64 crops) and
+configs[4] (EfficientNetV2-L, 384 px, 32 crops, 122 joints) through Pose3dEstimator.estimate_poses_batched,
+  A = the f32 folded copy under f16 autocast (bench.py's f16 mode, the reference's GPU arithmetic),
+  B = the f16 folded copy (backbones.fold_batchnorm(dtype=torch.float16): K13h, weights cast once),
+built from the same seeded network (bench.build_model), timed in interleaved pairs (A then B, --pairs times) with
+device events over --steps calls each, reported as crops/s, plus each arm's MPJPE to the f32 folded model on the
+same call (mm).  Both arms run with the estimator's API graphs as a user gets them (graph_batches 'auto': each
+internal batch shape is captured on its second call and replayed after; --graph-batches off for eager calls);
+the graph cache's replay counts are reported with each pair.  bench.py itself is only imported.
+
+    python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--config', type=int, default=1, choices=[1, 4])
+    ap.add_argument('--pairs', type=int, default=5)
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--dtype', choices=['f16', 'bf16'], default='f16')
+    ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
+    ap.add_argument('--out', required=True)
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    from metrabs_amd.backbones import fold_batchnorm
+    dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
+    argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype]
+    bargs = bench.parse_args()
+    sys.argv = argv
+    dev = torch.device('cuda')
+    est_a, _ = bench.build_model(bargs, dev)                     # f32 copy under 16-bit autocast
+    est_b, _ = bench.build_model(bargs, dev)                     # the same seeded network ...
+    est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt)
+    est_b.crop_dtype = est_b.crop_model.input_dtype              # ... as its 16-bit copy
+    est_f, _ = bench.build_model(bargs, dev)                     # f32 folded: the accuracy reference
+    est_f.crop_model.autocast_dtype = None
+    est_f.crop_dtype = torch.float32
+    for e in (est_a, est_b):
+        e.graph_batches = 'auto' if args.graph_batches == 'auto' else False
+    est_f.graph_batches = False
+
+    g = torch.Generator().manual_seed(5)
+    n_box, frames, im_h, im_w = bargs.batch, bargs.frames, 1080, 1920
+    images = torch.randint(0, 256, (frames, 3, im_h, im_w), dtype=torch.uint8, generator=g).to(dev)
+    bw = 60 + 340 * torch.rand(n_box, generator=g)
+    bh = 150 + 750 * torch.rand(n_box, generator=g)
+    bx = torch.rand(n_box, generator=g) * (im_w - bw)
+    by = torch.rand(n_box, generator=g) * (im_h - bh).clamp_min(1.0)
+    allb = torch.stack([bx, by, bw, bh], dim=1)
+    ids = (torch.arange(n_box) * frames) // n_box
+    boxes = [allb[ids == i] for i in range(frames)]
+    f = max(im_h, im_w) / (np.tan(np.deg2rad(55.0) / 2) * 2)
+    K = torch.tensor([[f, 0, im_w / 2], [0, f, im_h / 2], [0, 0, 1]], dtype=torch.float32).repeat(frames, 1, 1)
+
+    def call(est):
+        r = est.estimate_poses_batched(images, boxes, intrinsic_matrix=K, internal_batch_size=n_box,
+                                       num_aug=bargs.num_aug)
+        return torch.cat(r['poses3d'])
+
+    def timed(est):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(args.steps):
+            call(est)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return n_box * args.steps / (ev[0].elapsed_time(ev[1]) / 1e3)
+
+    rows = []
+    with torch.inference_mode():
+        p_f, p_a, p_b = call(est_f), call(est_a), call(est_b)
+        mpjpe = lambda p: float((p - p_f).norm(dim=-1).mean())
+        acc = dict(kind='accuracy', config=args.config, dtype=args.dtype, mpjpe_autocast_mm=round(mpjpe(p_a), 4),
+                   mpjpe_copy_mm=round(mpjpe(p_b), 4))
+        print(json.dumps(acc), flush=True)
+        rows.append(acc)
+        for _ in range(args.warmup):
+            call(est_a), call(est_b)
+        torch.cuda.synchronize()
+        for i in range(args.pairs):
+            a, b = timed(est_a), timed(est_b)
+            row = dict(kind='pair', config=args.config, dtype=args.dtype, graph_batches=args.graph_batches, pair=i,
+                       autocast_crops_per_s=round(a, 1), copy_crops_per_s=round(b, 1), gain=round(b / a - 1, 4),
+                       autocast_graph_replays=est_a.graphs.stats['replays'],
+                       copy_graph_replays=est_b.graphs.stats['replays'])
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        for r in rows:
+            fh.write(json.dumps(r) + '\n')
+
+
+if __name__ == '__main__':
+    main()

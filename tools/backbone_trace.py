@@ -16,8 +16,13 @@ last; `report` names each kernel's role in its block (SE fc1 / bias / act, fc2, 
 K10, K11, se_gate, ...) from that module and the kernel's name and writes a markdown table: per MBConv
 block the time of every role, the sum of the squeeze-excite tail, and per project shape the GEMM time.
 Marker kernels and the gaps they open are not counted; kernel durations are the tracer's.
+`record --precision` picks the arithmetic: f32 (the default, as above), f16-autocast / bf16-autocast (the f32
+copy under torch.autocast, 16-bit crops: bench.py's --precision f16 / bf16), f16-copy / bf16-copy (the 16-bit
+copy, fold_batchnorm(dtype=), 16-bit crops; unpinned like 16-bit autocast); `--backbone` / `--batch` / `--res`
+the network and shape (effnetv2-l, 32, 384: configs[4]).
 """
 import argparse
+import contextlib
 import csv
 import glob
 import json
@@ -38,12 +43,21 @@ def record(args):
     from metrabs_amd.backbones import build_backbone, calibrate_batchnorm, fold_batchnorm
     dev = torch.device('cuda')
     torch.manual_seed(1234)
-    torch.backends.cudnn.deterministic = True  # Metrabs.deterministic_backbone (on for f32)
-    net = build_backbone('effnetv2-s').to(dev)
+    dt = {'f32': None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.precision.split('-')[0]]
+    # Metrabs.deterministic_backbone: pinned for f32 only
+    torch.backends.cudnn.deterministic = dt is None
+    net = build_backbone(args.backbone).to(dev)
     calibrate_batchnorm(net, args.res, dev,
                         samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
-    net = fold_batchnorm(net.eval(), fused_epilogue=True)
+    net = fold_batchnorm(net.eval(), fused_epilogue=True,
+                         dtype=dt if args.precision.endswith('-copy') else None)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+    if dt is not None:
+        x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
+    # a fresh autocast region per forward, as Metrabs.forward enters one per call: autocast caches the weight
+    # casts of a region, so a region around several forwards would hide them from all but the first
+    mode = ((lambda: torch.autocast('cuda', dtype=dt)) if args.precision.endswith('-autocast')
+            else contextlib.nullcontext)
     order = []
 
     def hook(name):
@@ -54,10 +68,12 @@ def record(args):
 
     with torch.inference_mode():
         for _ in range(args.warmup):
-            net(x)
+            with mode():
+                net(x)
         torch.cuda.synchronize()
         handles = [m.register_forward_pre_hook(hook(n or '<root>')) for n, m in net.named_modules()]
-        feat = net(x)
+        with mode():
+            feat = net(x)
         torch.cuda.synchronize()
         for h in handles:
             h.remove()
@@ -68,7 +84,7 @@ def record(args):
     os.makedirs(os.path.dirname(os.path.abspath(args.markers)), exist_ok=True)
     with open(args.markers, 'w') as f:
         json.dump(dict(order=order, conv1x1=shapes, batch=args.batch, res=args.res,
-                       feature_shape=list(feat.shape)), f)
+                       feature_shape=list(feat.shape), precision=args.precision, backbone=args.backbone), f)
     print(f'recorded {len(order)} markers')
 
 
@@ -91,6 +107,8 @@ def _kind(kname):
         return 'marker'
     if 'se_gate' in k:
         return 'se_gate'
+    if 'conv1x1_16_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
+        return 'K13h'
     if 'conv1x1_kernel' in k:  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
         return 'K13'
     if 'bias_act' in k:
@@ -105,6 +123,8 @@ def _kind(kname):
         return 'silu'
     if 'mul' in k or 'binaryfunctor' in k:
         return 'binary'
+    if 'copy_kernel' in k:  # dtype casts (autocast's per-forward weight casts, .to(dtype))
+        return 'cast/copy'
     if 'miopen' in k or 'conv' in k:
         return 'conv'
     return 'other'
@@ -163,16 +183,17 @@ def report(args):
         if role is None:
             # the MBConv layers: '0' expand 1x1, '1' depthwise, '2' SE, '3' project
             role = {0: 'expand', 1: 'depthwise', 2: 'SE other', 3: 'project'}.get(layer, f'layer {layer}')
-            if role == 'project' and kind in ('gemm', 'conv', 'K13'):
+            if role == 'project' and kind in ('gemm', 'conv', 'K13', 'K13h'):
                 # (K13 runs inside the ConvBiasAct, the library GEMM inside its .conv)
                 proj[tuple(convs.get(module) or convs.get(module + '.conv', ('?',)))].append(us)
-            role = role if kind in ('gemm', 'conv', 'K11', 'K13') else f'{role} {kind}'
+            role = role if kind in ('gemm', 'conv', 'K11', 'K13', 'K13h') else f'{role} {kind}'
         b[role] += us
     tail_roles = ['SE fc1', 'SE fc1 bias', 'SE act', 'SE fc2', 'SE fc2 bias', 'SE gate fn', 'se_gate', 'x * gate',
                   'project', 'K10']
     roles = [r for r in tail_roles if any(r in b for b in blocks.values())]
     others = sorted({r for b in blocks.values() for r in b} - set(roles))
-    lines = [f'# Backbone per-layer kernel times: EfficientNetV2-S, batch {meta["batch"]}, {meta["res"]} px, f32',
+    lines = [f'# Backbone per-layer kernel times: {meta.get("backbone", "effnetv2-s")}, batch {meta["batch"]}, '
+             f'{meta["res"]} px, {meta.get("precision", "f32")}',
              '', f'{args.title}', '',
              f'One marked forward (tools/backbone_trace.py): {len(per_kernel)} kernels, {total:.1f} us of kernel '
              f'time (markers excluded).  Times in us.  "tail" = the squeeze-excite roles + x * gate + project + '
@@ -213,6 +234,9 @@ def main():
     r.add_argument('--batch', type=int, default=64)
     r.add_argument('--res', type=int, default=256)
     r.add_argument('--warmup', type=int, default=3)
+    r.add_argument('--backbone', default='effnetv2-s')
+    r.add_argument('--precision', default='f32',
+                   choices=['f32', 'f16-autocast', 'bf16-autocast', 'f16-copy', 'bf16-copy'])
     p = sub.add_parser('report')
     p.add_argument('--trace', required=True)
     p.add_argument('--markers', required=True)

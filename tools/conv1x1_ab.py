@@ -2,12 +2,20 @@
 """Per-shape A/B of the 1x1 convolutions of EfficientNetV2-S at the bench shape (batch 64, 256 px, f32):
 K13 (kernels.conv1x1_bias_act: one launch) against the path it replaces (x * gate where a squeeze-excite
 block hands one over, the library convolution under the deterministic pin bench.py uses, K10).
+--dtype f16 / bf16 times K13h (kernels.conv1x1_bias_act16) against rocBLAS f16 / bf16 + K10 (+ x * gate) on
+16-bit tensors instead; --backbone / --batch / --res pick the network and shape (effnetv2-l, 32, 384: configs[4]).
 
     python tools/conv1x1_ab.py --out OUT.jsonl      # on the GPU
 
 Shapes are read from a hooked forward of the folded network; each class (Cin, Cout, H, W, act, skip,
 gate) is timed with device events over --iters calls per arm, the two arms alternated in rounds, and
-reported as the median per-call time with its share of the 155 TF f32 MFMA peak and the HBM floor.
+reported as the median per-call time with its share of the MFMA peak (155 TF f32, 2.5 PF f16 / bf16) and of
+the HBM floor (one read of x, w and the skip, one write of y, at HBM_TBS: the measured copy bandwidth of an
+MI355X, 6.29 TB/s; the spec is 8.0).
+--timing graph (the 16-bit default) captures --iters calls of each arm in a HIP graph and times its replays:
+GPU time without the host's launch cost, as the estimator runs its graphed batches.  --timing eager (the f32
+default) times the calls as they are issued.  The library arm of a 16-bit run is unpinned (cudnn deterministic
+off), as the 16-bit copy runs by default; the f32 arm keeps the deterministic pin the f32 model runs under.
 """
 import argparse
 import json
@@ -15,13 +23,13 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAK_TF, HBM_TBS = 155.0, 5.0
+PEAK_TF, PEAK16_TF, HBM_TBS = 155.0, 2500.0, 6.29
 
 
-def shape_classes(batch, res):
+def shape_classes(batch, res, backbone='effnetv2-s'):
     import torch
     from metrabs_amd import backbones
-    net = backbones.fold_batchnorm(backbones.build_backbone('effnetv2-s').eval(), fused_epilogue=True).cuda()
+    net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True).cuda()
     out = {}
     for name, m in net.named_modules():
         if isinstance(m, backbones.ConvBiasAct) and m.conv.kernel_size == (1, 1) and m.conv.stride == (1, 1):
@@ -45,61 +53,98 @@ def main():
     ap.add_argument('--res', type=int, default=256)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--dtype', choices=['f32', 'f16', 'bf16'], default='f32')
+    ap.add_argument('--backbone', default='effnetv2-s')
+    ap.add_argument('--timing', choices=['graph', 'eager'], default=None,
+                    help='default: graph for f16 / bf16, eager for f32')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
     import torch.nn.functional as F
     from metrabs_amd import kernels
-    classes = shape_classes(args.batch, args.res)
+    classes = shape_classes(args.batch, args.res, args.backbone)
+    dt = {'f32': torch.float32, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
+    k = 'k13' if dt == torch.float32 else 'k13h'
+    peak = PEAK_TF if dt == torch.float32 else PEAK16_TF
+    timing = args.timing or ('eager' if dt == torch.float32 else 'graph')
+    pinned = dt == torch.float32
     rows = []
     g = torch.Generator(device='cuda').manual_seed(0)
     for (K, M, H, W, act, res, gated), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
         B = args.batch
-        x = torch.randn(B, K, H, W, device='cuda', generator=g)
-        w = torch.randn(M, K, 1, 1, device='cuda', generator=g) / K ** 0.5
+        x = torch.randn(B, K, H, W, device='cuda', generator=g).to(dt)
+        w = (torch.randn(M, K, 1, 1, device='cuda', generator=g) / K ** 0.5).to(dt)
         b = torch.randn(M, device='cuda', generator=g)
         gate = torch.rand(B, K, device='cuda', generator=g) if gated else None
-        r = torch.randn(B, M, H, W, device='cuda', generator=g) if res else None
-        y = torch.empty(B, M, H, W, device='cuda')
+        r = torch.randn(B, M, H, W, device='cuda', generator=g).to(dt) if res else None
+        y = torch.empty(B, M, H, W, device='cuda', dtype=dt)
 
         def old():
-            xi = x if gate is None else x * gate.view(B, K, 1, 1)
+            xi = x if gate is None else x * gate.to(dt).view(B, K, 1, 1)
             yy = F.conv2d(xi, w)
             kernels.bias_act_(yy, b, act, r)
             return yy
 
         def new():
+            if dt != torch.float32:
+                return kernels.conv1x1_bias_act16(x, w, b, act, gate=gate, residual=r, out=y)
             return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y)
+
+        def captured(fn):
+            """--iters calls of fn as one HIP graph (fn has run eagerly before: lazy set-up is done)."""
+            st = torch.cuda.Stream()
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                fn()
+                st.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=st, capture_error_mode='thread_local'):
+                    for _ in range(args.iters):
+                        fn()
+            torch.cuda.current_stream().wait_stream(st)
+            torch.cuda.synchronize()
+            return graph
 
         def timed(fn):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev[0].record()
-            for _ in range(args.iters):
-                fn()
+            if timing == 'graph':
+                fn.replay()
+            else:
+                for _ in range(args.iters):
+                    fn()
             ev[1].record()
             torch.cuda.synchronize()
             return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
 
-        with torch.inference_mode(), torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):
+        with torch.inference_mode(), torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=pinned):
             a, c = old(), new()
             torch.cuda.synchronize()
-            diff = float((a - c).abs().max() / a.abs().max().clamp_min(1e-30))
+            diff = float((a - c).abs().max().float() / a.abs().max().float().clamp_min(1e-30))
             for _ in range(3):
                 old(), new()
+            arm_old, arm_new = (captured(old), captured(new)) if timing == 'graph' else (old, new)
+            for _ in range(2):
+                timed(arm_old), timed(arm_new)
             t_old, t_new = [], []
             for _ in range(args.rounds):
-                t_old.append(timed(old))
-                t_new.append(timed(new))
+                t_old.append(timed(arm_old))
+                t_new.append(timed(arm_new))
+            del arm_old, arm_new
         med = lambda v: sorted(v)[len(v) // 2]
         flop = 2.0 * B * H * W * K * M
-        byts = 4.0 * (B * H * W * (K + M * (2 if res else 1)) + M * K)
-        floor = max(flop / (PEAK_TF * 1e12), byts / (HBM_TBS * 1e12)) * 1e6
+        byts = x.element_size() * (B * H * W * (K + M * (2 if res else 1)) + M * K)
+        byte_floor = byts / (HBM_TBS * 1e12) * 1e6
+        floor = max(flop / (peak * 1e12) * 1e6, byte_floor)
         row = dict(cin=K, cout=M, hw=f'{H}x{W}', act=act, skip=res, gate=gated, layers=len(names), first=names[0],
-                   old_us=round(med(t_old), 2), k13_us=round(med(t_new), 2),
-                   k13_tflops=round(flop / med(t_new) / 1e6, 1),
-                   k13_share_of_peak=round(flop / med(t_new) / 1e6 / PEAK_TF, 3), floor_us=round(floor, 2),
-                   speedup=round(med(t_old) / med(t_new), 3), rel_diff=diff)
+                   old_us=round(med(t_old), 2), **{f'{k}_us': round(med(t_new), 2),
+                                                   f'{k}_tflops': round(flop / med(t_new) / 1e6, 1),
+                                                   f'{k}_share_of_peak': round(flop / med(t_new) / 1e6 / peak, 3)},
+                   floor_us=round(floor, 2), speedup=round(med(t_old) / med(t_new), 3), rel_diff=diff)
+        if dt != torch.float32:
+            row.update(dtype=args.dtype, batch=B, res=args.res, timing=timing, library_pinned=pinned, hbm_tbs=HBM_TBS,
+                       byte_floor_us=round(byte_floor, 2), share_of_byte_floor=round(byte_floor / med(t_new), 3))
         rows.append(row)
         print(json.dumps(row), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
