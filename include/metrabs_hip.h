@@ -532,6 +532,29 @@ int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weight, const f
                            const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
                            int M, int K, int HW, void* y, mtr_stream_t stream);
 
+/* K14h (outside the reference's hot path, like K10): a dense 3x3 convolution of f16 / bf16 tensors -- stride 1 or
+ * 2, padding 1 on all sides, no dilation, groups 1 -- as one implicit 16-bit MFMA GEMM
+ * (v_mfma_f32_32x32x16_{f16,bf16}) with the K10 epilogue folded in:
+ *   y[b, m, oy, ox] = rnd16(act(bias[m] + sum_{ky, kx, ci} weight[m, ky, kx, ci]
+ *                                          * x[b, ci, stride oy + ky - 1, stride ox + kx - 1]) (+ residual[b, m, oy, ox]))
+ * x [B, Cin, H, W], y and residual [B, Cout, Ho, Wo] with Ho = (H - 1) / stride + 1, Wo likewise (NCHW, contiguous,
+ * 16-byte aligned), all in `dtype` (MTR_F16 or MTR_BF16, else MTR_E_DTYPE).  weight is the convolution weight
+ * REPACKED to [Cout][3][3][Cin] (torch: w.permute(0, 2, 3, 1).contiguous()), 16-byte aligned -- not OIHW: the
+ * reduction runs over (ky, kx, ci) with ci innermost.  bias [Cout] f32; residual may be NULL and may be x itself.
+ * The sum is accumulated in f32 in 16-k MFMA steps in that one k order, the epilogue is f32 in K10's order (act,
+ * then the residual), rounded to 16 bits once (to nearest even).  Cin a multiple of 8, W and Wo multiples of 4,
+ * and the input halo of one output tile (all Cin channels) must fit 160 KiB of LDS (Cin up to 256 at stride 1 and 120 at
+ * stride 2; mtr_conv3x3_16_lds_bytes tells),
+ * else MTR_E_SHAPE: the caller takes the library path.  y must not alias x or residual.  No atomics, no split-K:
+ * the same inputs give the same bits, whichever tile the shape picks. */
+int mtr_conv3x3_bias_act16(const void* x, int dtype, const void* weight /*[Cout][3][3][Cin]*/, const float* bias,
+                           const void* residual, int act, long long B, int Cin, int Cout, int H, int W, int stride,
+                           void* y, mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_conv3x3_bias_act16 uses for this shape (the staged input halo), or 0 where the
+ * entry has no kernel for it and answers MTR_E_SHAPE.  No GPU work. */
+size_t mtr_conv3x3_16_lds_bytes(long long B, int Cin, int Cout, int H, int W, int stride);
+
 #ifdef __cplusplus
 }
 #endif

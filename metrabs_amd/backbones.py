@@ -390,22 +390,87 @@ class ConvBiasAct(nn.Module):
         self.last_path = 'library'
         if gate is not None:  # (not reached when the gate was handed over: k13_takes(x) was checked)
             x = x * gate.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
-        y = self.conv(x)
-        # K10 moves 16 bytes per lane: planes of a multiple of the vector width (7x7 maps at 224 px,
-        # 5x5 at 160 px are not), 16-byte aligned storage; everything else takes the torch ops
-        hw_vec_ok = (y.shape[2] * y.shape[3]) % (16 // y.element_size()) == 0
-        if y.is_cuda and y.is_contiguous() and hw_vec_ok and y.data_ptr() % 16 == 0 and (
-                residual is None or (residual.dtype == y.dtype and residual.is_contiguous()
-                                     and residual.data_ptr() % 16 == 0)):
+        return _library_conv_bias_act(self, x, residual)
+
+
+def _library_conv_bias_act(mod, x, residual):
+    """The library path of a folded convolution `mod` (ConvBiasAct, Conv3x3BiasAct): mod.conv (MIOpen / rocBLAS),
+    then "+ bias, activation (, + residual)" as K10 where it applies, else the torch ops."""
+    y = mod.conv(x)
+    # K10 moves 16 bytes per lane: planes of a multiple of the vector width (7x7 maps at 224 px,
+    # 5x5 at 160 px are not), 16-byte aligned storage; everything else takes the torch ops
+    hw_vec_ok = (y.shape[2] * y.shape[3]) % (16 // y.element_size()) == 0
+    if y.is_cuda and y.is_contiguous() and hw_vec_ok and y.data_ptr() % 16 == 0 and (
+            residual is None or (residual.dtype == y.dtype and residual.is_contiguous()
+                                 and residual.data_ptr() % 16 == 0)):
+        from . import kernels
+        if getattr(mod, 'emit_mean', False) and residual is None:
+            y, mean = kernels.bias_act_rowmean_(y, mod.bias, mod.act_name)
+            mod._mean = (y, mean)
+            return y
+        return kernels.bias_act_(y, mod.bias, mod.act_name, residual)
+    y = y + mod.bias.view(1, -1, 1, 1).to(y.dtype)
+    y = y if mod.act is None else mod.act(y)
+    return y if residual is None else residual + y
+
+
+class Conv3x3BiasAct(nn.Module):
+    """A folded dense 3x3 conv + BN (+ activation) of a 16-bit copy (fold_batchnorm(dtype=)): the convolution,
+    "+ bias", the activation and the block's skip as ONE HIP launch on the matrix cores (K14h, conv3x3_16.hip)
+    instead of a MIOpen convolution followed by K10.  It keeps the folded `conv` (16-bit weight) for every input
+    K14h does not take -- channels_last, CPU, autocast, odd maps, a gradient wanted -- which then runs exactly
+    what ConvBiasAct runs."""
+
+    # class-wide switch (tests and A/B runs): the library path everywhere
+    use_k14h = True
+    # (Cin, Cout, stride, H, W) of the input where K14h measured slower than MIOpen (unpinned, as the copy runs) +
+    # K10 in f16 or bf16, both timed as HIP graph replays (EfficientNetV2-S and ResNet-18 batch 64 at 256 px,
+    # EfficientNetV2-L batch 32 at 384 px; DESIGN.md section 13, profiles/r10a_conv3x3_ab_*.jsonl)
+    k14h_slower = frozenset({(64, 256, 2, 96, 96), (64, 64, 1, 64, 64)})
+
+    def __init__(self, conv, bias, act):
+        super().__init__()
+        self.conv = conv
+        from . import kernels
+        self.register_buffer('weight_packed', kernels.pack_conv3x3_weight(conv.weight))  # [Cout, 3, 3, Cin]
+        self.register_buffer('bias', bias.detach().float().contiguous())
+        self.act = act
+        self.act_name = None if act is None else _ACT_NAMES[type(act)]
+        self.stride = conv.stride[0]
+        self.last_path = None  # 'k14h' or 'library': what the last forward ran (tests, A/B runs)
+
+    @staticmethod
+    def applies_to(conv):
+        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
+                and conv.dilation == (1, 1) and conv.stride in ((1, 1), (2, 2)) and conv.padding == (1, 1)
+                and conv.padding_mode == 'zeros' and conv.in_channels % 8 == 0)
+
+    def k14h_takes(self, x):
+        """Whether forward(x) runs on K14h: a CUDA NCHW-contiguous input of the copy's dtype, autocast off, no
+        gradient wanted, a shape the C entry accepts and that is not listed as slower."""
+        c = self.conv
+        if not (Conv3x3BiasAct.use_k14h and x.is_cuda and x.dim() == 4 and x.dtype == c.weight.dtype
+                and x.dtype in (torch.float16, torch.bfloat16) and c.bias is None):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
+            return False
+        if (c.in_channels, c.out_channels, self.stride, x.shape[2], x.shape[3]) in Conv3x3BiasAct.k14h_slower:
+            return False
+        from . import kernels
+        return kernels.conv3x3_16_supported(x, self.weight_packed, self.stride)
+
+    def forward(self, x, residual=None):
+        w16 = self.conv.weight.dtype
+        if x.dtype != w16 and w16 in (torch.float16, torch.bfloat16) and not torch.is_autocast_enabled(x.device.type):
+            x = x.to(w16)  # the first convolution of a 16-bit copy: the input is cast once, here
+        if self.k14h_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                                        and residual.data_ptr() % 16 == 0)):
             from . import kernels
-            if self.emit_mean and residual is None:
-                y, mean = kernels.bias_act_rowmean_(y, self.bias, self.act_name)
-                self._mean = (y, mean)
-                return y
-            return kernels.bias_act_(y, self.bias, self.act_name, residual)
-        y = y + self.bias.view(1, -1, 1, 1).to(y.dtype)
-        y = y if self.act is None else self.act(y)
-        return y if residual is None else residual + y
+            self.last_path = 'k14h'
+            return kernels.conv3x3_bias_act16(x, self.weight_packed, self.bias, self.act_name, self.stride,
+                                              residual=residual)
+        self.last_path = 'library'
+        return _library_conv_bias_act(self, x, residual)
 
 
 class DepthwiseBiasAct(nn.Module):
@@ -459,11 +524,11 @@ class DepthwiseBiasAct(nn.Module):
 
 
 def _block_plus_skip(block, x):
-    """x + block(x) of an (Fused)MBConv; when the block ends in a folded convolution (ConvBiasAct)
-    the skip connection rides on its epilogue instead of being a kernel of its own."""
+    """x + block(x) of an (Fused)MBConv; when the block ends in a folded convolution (ConvBiasAct,
+    Conv3x3BiasAct) the skip connection rides on its epilogue instead of being a kernel of its own."""
     last = block[-1]
     tail = last[0] if isinstance(last, ConvBNAct) else None
-    if isinstance(tail, ConvBiasAct):
+    if isinstance(tail, (ConvBiasAct, Conv3x3BiasAct)):
         y = x
         for m in list(block)[:-1]:
             y = m(y)
@@ -486,7 +551,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
     norms are folded in f32, then every convolution weight that runs as a GEMM or MIOpen convolution (1x1, dense
     3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise layers (K11) and the
     squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast at the first
-    convolution; run it with autocast off) and its 1x1 stride-1 convolutions run on K13h."""
+    convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense 3x3 convolutions
+    (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -548,6 +614,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
         for m in folded.modules():
             if isinstance(m, ConvBiasAct):
                 m.conv.to(dtype)
+        for m in folded.modules():  # the dense 3x3 layers: K14h, on the weight repacked once
+            if isinstance(m, ConvBNAct) and isinstance(m[0], ConvBiasAct) and not m[0].emit_mean \
+                    and Conv3x3BiasAct.applies_to(m[0].conv):
+                m[0] = Conv3x3BiasAct(m[0].conv, m[0].bias, m[0].act)
         folded.inference_dtype = dtype
     return folded
 

@@ -733,3 +733,61 @@ def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None):
         None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
         ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act16')
     return out
+
+
+# K14h: a dense 3x3 convolution of f16 / bf16 tensors as one implicit 16-bit MFMA GEMM (csrc/conv3x3_16.hip)
+
+def pack_conv3x3_weight(weight):
+    """The [Cout, Cin, 3, 3] convolution weight as mtr_conv3x3_bias_act16 takes it: [Cout, 3, 3, Cin], contiguous
+    (the reduction runs over (ky, kx, ci) with ci innermost).  Plain torch; done once, at fold time."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f'pack_conv3x3_weight: expected [Cout, Cin, 3, 3], got {tuple(weight.shape)}')
+    return weight.detach().permute(0, 2, 3, 1).contiguous()
+
+
+def conv3x3_16_supported(x, weight, stride):
+    """Whether mtr_conv3x3_bias_act16 takes this input: f16 or bf16 x and weight of one dtype, x NCHW-contiguous and
+    16-byte aligned, stride 1 or 2, Cin a multiple of 8, the input and output widths multiples of 4, the input
+    halo of a tile within LDS (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).
+    `weight` is the convolution weight, [Cout, Cin, 3, 3] or packed [Cout, 3, 3, Cin]."""
+    if x.dim() != 4 or weight.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) \
+            or weight.dtype != x.dtype or not x.is_contiguous() or x.data_ptr() % 16 or weight.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if weight.numel() != weight.shape[0] * K * 9 or B >= 2 ** 16:
+        return False
+    return _lib.load().mtr_conv3x3_16_lds_bytes(B, K, weight.shape[0], H, W, int(stride)) > 0
+
+
+def conv3x3_bias_act16(x, w_packed, bias, act, stride, residual=None, out=None):
+    """y = act(conv3x3(x, w, stride, padding 1) + bias) (+ residual) in one launch on the current stream, for
+    f16 / bf16: x [B, Cin, H, W] NCHW-contiguous, w_packed [Cout, 3, 3, Cin] (pack_conv3x3_weight) in x's dtype,
+    bias [Cout] f32, residual [B, Cout, Ho, Wo] in x's dtype or None.  f32 accumulation in a fixed k order,
+    rounded to x's dtype once (the same bits on every call and graph replay)."""
+    require_cuda(x, w_packed, bias, residual)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('conv3x3_bias_act16: x must be [B, Cin, H, W], NCHW-contiguous')
+    B, K, H, W = x.shape
+    M = w_packed.shape[0]
+    if w_packed.dim() != 4 or tuple(w_packed.shape[1:]) != (3, 3, K) or not w_packed.is_contiguous():
+        raise ValueError(f'conv3x3_bias_act16: the weight must be packed [Cout, 3, 3, {K}] and contiguous, '
+                         f'got {tuple(w_packed.shape)}')
+    if w_packed.dtype != x.dtype:
+        raise ValueError(f'conv3x3_bias_act16: weight is {w_packed.dtype}, x is {x.dtype}')
+    if stride not in (1, 2):
+        raise ValueError(f'conv3x3_bias_act16: stride must be 1 or 2, got {stride}')
+    if bias.numel() != M:
+        raise ValueError(f'conv3x3_bias_act16: bias has {bias.numel()} elements, expected {M}')
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if residual is not None and (residual.shape != (B, M, Ho, Wo) or residual.dtype != x.dtype
+                                 or not residual.is_contiguous()):
+        raise ValueError('conv3x3_bias_act16: residual must be [B, Cout, Ho, Wo] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, Ho, Wo, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, Ho, Wo) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('conv3x3_bias_act16: out must be [B, Cout, Ho, Wo] like the output, contiguous')
+    check(_lib.load().mtr_conv3x3_bias_act16(
+        _ptr(x), dtype_code(x.dtype), _ptr(w_packed), _ptr(bias.contiguous().float()),
+        None if residual is None else _ptr(residual), ACT_CODES[act], B, K, M, H, W, int(stride), _ptr(out),
+        current_stream_ptr(x.device)), 'mtr_conv3x3_bias_act16')
+    return out

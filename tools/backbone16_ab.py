@@ -8,6 +8,9 @@ device events over --steps calls each, reported as crops/s, plus each arm's MPJP
 same call (mm).  Both arms run with the estimator's API graphs as a user gets them (graph_batches 'auto': each
 internal batch shape is captured on its second call and replayed after; --graph-batches off for eager calls);
 the graph cache's replay counts are reported with each pair.  bench.py itself is only imported.
+--ab k14h compares the 16-bit copy with itself instead: A = Conv3x3BiasAct.use_k14h off (the dense 3x3 layers on MIOpen
++ K10), B = on (K14h); the same tree and weights, so the pairs isolate K14h.  The rows keep their field names
+(autocast_* = arm A, copy_* = arm B) and carry ab='k14h'.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -27,13 +30,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
+    ap.add_argument('--ab', choices=['copy', 'k14h'], default='copy',
+                    help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
     import bench
-    from metrabs_amd.backbones import fold_batchnorm
+    from metrabs_amd.backbones import Conv3x3BiasAct, fold_batchnorm
     dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
     argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype]
     bargs = bench.parse_args()
@@ -43,6 +48,9 @@ def main():
     est_b, _ = bench.build_model(bargs, dev)                     # the same seeded network ...
     est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt)
     est_b.crop_dtype = est_b.crop_model.input_dtype              # ... as its 16-bit copy
+    if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
     est_f, _ = bench.build_model(bargs, dev)                     # f32 folded: the accuracy reference
     est_f.crop_model.autocast_dtype = None
     est_f.crop_dtype = torch.float32
@@ -64,6 +72,8 @@ def main():
     K = torch.tensor([[f, 0, im_w / 2], [0, f, im_h / 2], [0, 0, 1]], dtype=torch.float32).repeat(frames, 1, 1)
 
     def call(est):
+        # the class switch is read when a forward runs eagerly or is captured; a replayed graph keeps its arm
+        Conv3x3BiasAct.use_k14h = not (args.ab == 'k14h' and est is est_a)
         r = est.estimate_poses_batched(images, boxes, intrinsic_matrix=K, internal_batch_size=n_box,
                                        num_aug=bargs.num_aug)
         return torch.cat(r['poses3d'])
@@ -90,7 +100,7 @@ def main():
         torch.cuda.synchronize()
         for i in range(args.pairs):
             a, b = timed(est_a), timed(est_b)
-            row = dict(kind='pair', config=args.config, dtype=args.dtype, graph_batches=args.graph_batches, pair=i,
+            row = dict(kind='pair', ab=args.ab, config=args.config, dtype=args.dtype, graph_batches=args.graph_batches, pair=i,
                        autocast_crops_per_s=round(a, 1), copy_crops_per_s=round(b, 1), gain=round(b / a - 1, 4),
                        autocast_graph_replays=est_a.graphs.stats['replays'],
                        copy_graph_replays=est_b.graphs.stats['replays'])

@@ -107,6 +107,8 @@ def _kind(kname):
         return 'marker'
     if 'se_gate' in k:
         return 'se_gate'
+    if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
+        return 'K14h'
     if 'conv1x1_16_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
         return 'K13h'
     if 'conv1x1_kernel' in k:  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
@@ -149,6 +151,48 @@ def _role(module, kind):
     return None
 
 
+def _fused_table(per_kernel, pat):
+    """The FusedMBConv stages (1 - 3) and the stem: per block the dense 3x3 convolution (MIOpen's kernels, layout
+    transposes and casts included, or K14h), the K10 pass behind it and the 1x1 project with its epilogue."""
+    rows = OrderedDict()
+    served = defaultdict(float)   # what serves the dense convolutions: kernel name (shortened) -> us
+    for module, kind, kname, us in per_kernel:
+        m = pat.match(module)
+        if m and int(m.group(1)) < 4:
+            key, layer = f'{m.group(1)}.{m.group(2)}', int(m.group(3))
+        elif module.startswith('1.0.') or module == '1.0':
+            key, layer = 'stem', 0
+        else:
+            continue
+        b = rows.setdefault(key, defaultdict(float))
+        if layer == 0:
+            col = 'K14h' if kind == 'K14h' else 'K10' if kind == 'K10' else 'dense conv'
+            if col == 'dense conv' and key != 'stem':
+                served[f'{kind}: {kname[:60]}'] += us
+        else:
+            col = 'project'   # (K13h, or the library GEMM + K10)
+        b[col] += us
+    cols = ['dense conv', 'K14h', 'K10', 'project']
+    lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project', '',
+             '| stage.block | ' + ' | '.join(cols) + ' | **3x3 + K10** |', '|---|' + '---|' * (len(cols) + 1)]
+    sums = defaultdict(float)
+    for key, b in rows.items():
+        dense = b['dense conv'] + b['K14h'] + b['K10']
+        for c in cols:
+            sums[c] += b[c]
+        sums['dense'] += dense
+        if key != 'stem':
+            sums['dense_blocks'] += dense
+        lines.append(f'| {key} | ' + ' | '.join(f'{b[c]:.1f}' for c in cols) + f' | **{dense:.1f}** |')
+    lines.append('| **sum** | ' + ' | '.join(f'{sums[c]:.1f}' for c in cols) + f' | **{sums["dense"]:.1f}** |')
+    lines += ['', f'Dense 3x3 layers of stages 1 - 3 with their epilogue (without the stem): '
+                  f'**{sums["dense_blocks"]:.1f} us**.']
+    if served:
+        lines += ['', 'Library kernels behind the "dense conv" column of stages 1 - 3 (kind: kernel, us):', '']
+        lines += [f'- `{k}` {v:.1f}' for k, v in sorted(served.items(), key=lambda kv: -kv[1])[:8]]
+    return lines
+
+
 def report(args):
     meta = json.load(open(args.markers))
     order = meta['order']
@@ -165,6 +209,7 @@ def report(args):
             per_kernel.append((order[j], _kind(r[2]), r[2], (r[1] - r[0]) / 1e3))
     total = sum(k[3] for k in per_kernel)
     pat = re.compile(r'^1\.(\d+)\.(\d+)\.block\.(\d+)')
+    fused = _fused_table(per_kernel, pat)
     blocks = OrderedDict()
     proj = defaultdict(list)
     convs = meta['conv1x1']
@@ -216,6 +261,7 @@ def report(args):
               '## Project GEMMs by shape (Cin -> Cout)', '', '| Cin -> Cout | calls | avg us | sum us |', '|---|---|---|---|']
     for shape, v in sorted(proj.items()):
         lines.append(f'| {" -> ".join(map(str, shape))} | {len(v)} | {sum(v) / len(v):.1f} | {sum(v):.1f} |')
+    lines += fused
     kinds = defaultdict(float)
     for _, kind, _, us in per_kernel:
         kinds[kind] += us

@@ -1,0 +1,151 @@
+#!/usr/bin/env python
+"""Per-shape A/B of the dense 3x3 convolutions of a 16-bit backbone copy at a bench shape (EfficientNetV2-S, batch 64,
+256 px by default; --backbone effnetv2-l --batch 32 --res 384 is configs[4]; --backbone resnet18 works too):
+K14h (kernels.conv3x3_bias_act16: one launch) against the path it replaces, the MIOpen convolution (unpinned, as
+the 16-bit copy runs) followed by K10 (bias, activation, skip).
+
+    python tools/conv3x3_ab.py --dtype f16 --out OUT.jsonl      # on the GPU
+
+The method is tools/conv1x1_ab.py's: shape classes (Cin, Cout, H, W, stride, act, skip) are read from a hooked
+forward of the folded copy; each arm is captured as a HIP graph of --iters calls and its replays are timed with
+device events, the two arms alternated in --rounds rounds, the median per-call time reported with its share of
+the 16-bit MFMA peak (2.5 PF) and of the byte floor (one 16-bit read of x, w and the skip, one write of y, at the
+measured 6.29 TB/s copy rate of an MI355X).  Shapes the C entry declines are reported with k14h_us null.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAK16_TF, HBM_TBS = 2500.0, 6.29
+
+
+def shape_classes(res, backbone, dtype):
+    import torch
+    from metrabs_amd import backbones
+    net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True, dtype=dtype).cuda()
+    out = {}
+    for name, m in net.named_modules():
+        if isinstance(m, backbones.Conv3x3BiasAct):
+            def hook(mod, args, kwargs, name=name):
+                x = args[0]
+                key = (x.shape[1], mod.conv.out_channels, x.shape[2], x.shape[3], mod.stride, mod.act_name,
+                       kwargs.get('residual') is not None)
+                out.setdefault(key, []).append(name)
+            m.register_forward_pre_hook(hook, with_kwargs=True)
+    backbones.Conv3x3BiasAct.use_k14h = False
+    with torch.inference_mode():
+        net(torch.rand(1, 3, res, res, device='cuda'))
+    backbones.Conv3x3BiasAct.use_k14h = True
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--res', type=int, default=256)
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--dtype', choices=['f16', 'bf16'], default='f16')
+    ap.add_argument('--backbone', default='effnetv2-s')
+    ap.add_argument('--out', required=True)
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import torch
+    import torch.nn.functional as F
+    from metrabs_amd import kernels
+    dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
+    classes = shape_classes(args.res, args.backbone, dt)
+    rows = []
+    g = torch.Generator(device='cuda').manual_seed(0)
+    for (K, M, H, W, stride, act, res), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+        B = args.batch
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        x = torch.randn(B, K, H, W, device='cuda', generator=g).to(dt)
+        w = (torch.randn(M, K, 3, 3, device='cuda', generator=g) / (9 * K) ** 0.5).to(dt)
+        wp = kernels.pack_conv3x3_weight(w)
+        b = torch.randn(M, device='cuda', generator=g)
+        r = torch.randn(B, M, Ho, Wo, device='cuda', generator=g).to(dt) if res else None
+        y = torch.empty(B, M, Ho, Wo, device='cuda', dtype=dt)
+        supported = kernels.conv3x3_16_supported(x, wp, stride)
+
+        def old():
+            yy = F.conv2d(x, w, None, stride, 1)
+            kernels.bias_act_(yy, b, act, r)
+            return yy
+
+        def new():
+            return kernels.conv3x3_bias_act16(x, wp, b, act, stride, residual=r, out=y)
+
+        def captured(fn):
+            """--iters calls of fn as one HIP graph (fn has run eagerly before: lazy set-up is done)."""
+            st = torch.cuda.Stream()
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                fn()
+                st.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=st, capture_error_mode='thread_local'):
+                    for _ in range(args.iters):
+                        fn()
+            torch.cuda.current_stream().wait_stream(st)
+            torch.cuda.synchronize()
+            return graph
+
+        def timed(graph):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            graph.replay()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
+
+        med = lambda v: sorted(v)[len(v) // 2]
+        with torch.inference_mode(), torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=False):
+            a = old()
+            diff = None
+            if supported:
+                c = new()
+                torch.cuda.synchronize()
+                diff = float((a - c).abs().max().float() / a.abs().max().float().clamp_min(1e-30))
+            for _ in range(3):
+                old()
+                if supported:
+                    new()
+            arm_old = captured(old)
+            arm_new = captured(new) if supported else None
+            for _ in range(2):
+                timed(arm_old)
+                if supported:
+                    timed(arm_new)
+            t_old, t_new = [], []
+            for _ in range(args.rounds):
+                t_old.append(timed(arm_old))
+                if supported:
+                    t_new.append(timed(arm_new))
+            del arm_old, arm_new
+        flop = 2.0 * B * Ho * Wo * 9 * K * M
+        byts = 2 * (B * (H * W * K + Ho * Wo * M * (2 if res else 1)) + 9 * M * K)
+        byte_floor = byts / (HBM_TBS * 1e12) * 1e6
+        row = dict(cin=K, cout=M, hw=f'{H}x{W}', stride=stride, act=act, skip=res, layers=len(names), first=names[0],
+                   dtype=args.dtype, batch=B, res=args.res, backbone=args.backbone, gflop=round(flop / 1e9, 2),
+                   mbytes=round(byts / 1e6, 1), old_us=round(med(t_old), 2),
+                   old_tflops=round(flop / med(t_old) / 1e6, 1), k14h_us=None)
+        if supported:
+            t = med(t_new)
+            row.update(k14h_us=round(t, 2), k14h_tflops=round(flop / t / 1e6, 1),
+                       k14h_share_of_peak=round(flop / t / 1e6 / PEAK16_TF, 3), byte_floor_us=round(byte_floor, 2),
+                       share_of_byte_floor=round(byte_floor / t, 3), speedup=round(med(t_old) / t, 3),
+                       k14h_us_range=[round(min(t_new), 2), round(max(t_new), 2)],
+                       old_us_range=[round(min(t_old), 2), round(max(t_old), 2)], rel_diff=diff)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        for r in rows:
+            f.write(json.dumps(r) + '\n')
+
+
+if __name__ == '__main__':
+    main()
