@@ -495,6 +495,24 @@ int mtr_depthwise3x3_bias_act_padded(const void* x, int dtype, const float* weig
                                      int pad_left, int pad_bottom, int pad_right, void* y,
                                      float* row_mean, mtr_stream_t stream);
 
+/* K15 (outside the reference's hot path, like K10 / K11): depthwise 5x5 convolution of the backbone's
+ * inference copy with the K10 epilogue in the same pass -- the 5x5 layers of MobileNetV3-Large
+ * (mobilenet_v3.py:387-432) and of the EfficientNet-B family (efficientnet.py:389-395).  K11's contract:
+ * x [B, C, H, W] -> y [B, C, OH, OW] (NCHW, same dtype, f32 / f16 / bf16), cross-correlation with
+ * weight [C, 5, 5] f32, bias [C] f32, zero padding pad_top, pad_left in 0..2 and pad_bottom, pad_right in
+ * 0..3 (symmetric 2, or the explicit TF-'SAME' / `bottomright_stride` padding (1, 3, 1, 3) folded in),
+ * stride in {1, 2}; OH = (H + pad_top + pad_bottom - 5) / stride + 1, OW likewise and a multiple of 4;
+ * y 16-byte aligned.  y = rnd(act(conv + bias[c])): f32 accumulation from 0 over (ky, kx) with ky outer,
+ * then the bias, the activation and one rounding, the same bits on every internal path (aligned or
+ * unaligned x), call and graph replay; no atomics.  row_mean (may be NULL): [B*C] f32 mean of the stored
+ * (rounded) result per plane.  The padded plane may be at most 112 x 112 (it is staged through LDS):
+ * larger ones return MTR_E_SHAPE.  Error codes in the order of mtr_depthwise3x3_bias_act_padded; B == 0
+ * returns MTR_OK without a launch.  Only enqueues on `stream`. */
+int mtr_depthwise5x5_bias_act_padded(const void* x, int dtype, const float* weight /*[C][5][5]*/,
+                                     const float* bias, int act, long long B, int C, int H, int W,
+                                     int stride, int pad_top, int pad_left, int pad_bottom, int pad_right,
+                                     void* y, float* row_mean /*[B*C] or NULL*/, mtr_stream_t stream);
+
 /* K12 (outside the reference's hot path, like K10): the squeeze-excite gate of an MBConv block
  * (efficientnet.py:110-173, torchvision SqueezeExcitation) in one launch, from the [B, C] f32 channel
  * mean K10 / K11 emit:

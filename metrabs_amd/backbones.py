@@ -474,15 +474,24 @@ class Conv3x3BiasAct(nn.Module):
 
 
 class DepthwiseBiasAct(nn.Module):
-    """A folded depthwise 3x3 conv + BN + activation as ONE HIP pass over the plane (K11): the
+    """A folded depthwise 3x3 (K11) or 5x5 (K15) conv + BN + activation as ONE HIP pass over the plane: the
     convolution, "+ bias", the activation and -- in front of a squeeze-excite block -- the
     per-channel mean, instead of PyTorch's depthwise kernel followed by K10.  Other tensors (CPU,
-    non-contiguous, widths that are not a multiple of 4) take the torch ops."""
+    non-contiguous, widths that are not a multiple of 4; for 5x5 also padded planes above 112 x 112 and the shapes
+    in k15_slower) take the torch ops at the layer's own kernel size and padding."""
+
+    # kernel sizes fold_batchnorm hands to this class (read at fold time: tests and A/B runs set (3,) to get
+    # the 5x5 layers as ConvBiasAct around DepthwiseConv2d, the module tree from before K15)
+    kernel_sizes = (3, 5)
+    # (C, H, W, stride) of the input where K15 measured slower than PyTorch's depthwise kernel + K10: these
+    # run the torch ops (DESIGN.md section 14)
+    k15_slower = frozenset()
 
     def __init__(self, conv, bias, act):
         super().__init__()
         self.weight = nn.Parameter(conv.weight.detach().float().contiguous(), requires_grad=False)
         self.register_buffer('bias', bias.detach().float().contiguous())
+        self.k = conv.kernel_size[0]
         self.stride, self.pad = conv.stride[0], conv.padding[0]
         # (left, right, top, bottom) of a ZeroPad2d that stood in front of the layer and was folded
         # in by fold_batchnorm (the TF-'SAME' padding of the stride-2 layers); None: self.pad all round
@@ -491,31 +500,40 @@ class DepthwiseBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False
         self._mean = None
+        self.last_path = None  # 'k11', 'k15' or 'library': what the last forward ran (tests, A/B runs)
 
-    @staticmethod
-    def applies_to(conv):
+    @classmethod
+    def applies_to(cls, conv):
+        k = conv.kernel_size[0] if isinstance(conv, nn.Conv2d) else None
         return (isinstance(conv, nn.Conv2d) and conv.groups == conv.in_channels == conv.out_channels
-                and conv.groups > 1 and conv.kernel_size == (3, 3) and conv.dilation == (1, 1)
-                and conv.stride in ((1, 1), (2, 2)) and conv.padding in ((0, 0), (1, 1))
-                and conv.padding_mode == 'zeros')
+                and conv.groups > 1 and k in cls.kernel_sizes and conv.kernel_size == (k, k)
+                and conv.dilation == (1, 1) and conv.stride in ((1, 1), (2, 2))
+                and conv.padding in ((0, 0), (k // 2, k // 2)) and conv.padding_mode == 'zeros')
 
     take_mean = ConvBiasAct.take_mean
     take_mean_f32 = ConvBiasAct.take_mean_f32
 
     def forward(self, x):
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
-        ow = (x.shape[3] + pl + pr - 3) // self.stride + 1
+        ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
         pad = self.pad if self.pads is None else self.pads
         if x.is_cuda and x.is_contiguous() and ow % 4 == 0 and \
                 x.dtype in (torch.float32, torch.float16, torch.bfloat16):
             from . import kernels
-            if self.emit_mean:
-                y, mean = kernels.depthwise3x3_bias_act(x, self.weight, self.bias, self.act_name,
-                                                        self.stride, pad, want_mean=True)
-                self._mean = (y, mean)
-                return y
-            return kernels.depthwise3x3_bias_act(x, self.weight, self.bias, self.act_name,
-                                                 self.stride, pad)
+            if self.k == 3:
+                fn, self.last_path = kernels.depthwise3x3_bias_act, 'k11'
+            elif (x.shape[1], x.shape[2], x.shape[3], self.stride) not in DepthwiseBiasAct.k15_slower and \
+                    kernels.depthwise5x5_supported(x.shape[2], x.shape[3], pad):
+                fn, self.last_path = kernels.depthwise5x5_bias_act, 'k15'
+            else:
+                fn = None
+            if fn is not None:
+                if self.emit_mean:
+                    y, mean = fn(x, self.weight, self.bias, self.act_name, self.stride, pad, want_mean=True)
+                    self._mean = (y, mean)
+                    return y
+                return fn(x, self.weight, self.bias, self.act_name, self.stride, pad)
+        self.last_path = 'library'
         if self.pads is not None:
             x = F.pad(x, self.pads)
         y = F.conv2d(x, self.weight.to(x.dtype), self.bias.to(x.dtype), self.stride,
@@ -549,10 +567,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
     in-place HIP pass (ConvBiasAct) instead of PyTorch-ROCm's two elementwise kernels.
     dtype=torch.float16 / torch.bfloat16 (needs fused_epilogue=True) returns a 16-bit inference copy: the batch
     norms are folded in f32, then every convolution weight that runs as a GEMM or MIOpen convolution (1x1, dense
-    3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise layers (K11) and the
-    squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast at the first
-    convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense 3x3 convolutions
-    (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h."""
+    3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise 3x3 and 5x5 layers (K11,
+    K15) and the squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast
+    at the first convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense
+    3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -577,7 +595,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
             m[1] = nn.Identity()
     if any(isinstance(m, nn.BatchNorm2d) for m in folded.modules()):
         raise ValueError('a BatchNorm2d outside a ConvBNAct block cannot be folded here')
-    if fused_epilogue:  # ZeroPad2d -> depthwise 3x3: the padding becomes an argument of K11
+    if fused_epilogue:  # ZeroPad2d -> depthwise 3x3 / 5x5: the padding becomes an argument of K11 / K15
         for seq in folded.modules():
             if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
                 continue
@@ -587,7 +605,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
                 if isinstance(pad, nn.ZeroPad2d) and isinstance(blk, ConvBNAct) and \
                         isinstance(blk[0], DepthwiseBiasAct) and blk[0].pad == 0:
                     l, r, t, b = (int(p) for p in pad.padding)
-                    if 0 <= l <= 1 and 0 <= t <= 1 and 0 <= r <= 2 and 0 <= b <= 2:
+                    lo, hi = blk[0].k // 2, blk[0].k // 2 + 1  # what the C entries take: 1 / 2 (3x3), 2 / 3 (5x5)
+                    if 0 <= l <= lo and 0 <= t <= lo and 0 <= r <= hi and 0 <= b <= hi:
                         blk[0].pads = (l, r, t, b)
                         seq._modules[n_pad] = nn.Identity()
     if fused_epilogue:  # conv -> squeeze-excite: the epilogue pass also emits the channel means

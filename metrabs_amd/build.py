@@ -21,7 +21,11 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-
 # per-source extras.  head_rt.hip: MFMA accumulators in VGPRs (gfx950's register file is unified):
 # its f32 chains are carried into f64 on the VALU every stage, and from AGPRs every element costs a
 # v_accvgpr_read first.
-EXTRA_FLAGS = {'head_rt.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1']}
+# depthwise5x5.hip: the SLP vectoriser pairs the 400 fma of a 4x4 output block into v_pk_fma_f32 and then needs 195
+# (f32) to 267 (16-bit) VGPRs for the shuffled operands -- one or two waves per SIMD, and spills when bounded to
+# four; without it the kernels take 113 - 118 VGPRs and no scratch.
+EXTRA_FLAGS = {'head_rt.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
+               'depthwise5x5.hip': ['-fno-slp-vectorize']}
 
 
 def sources():

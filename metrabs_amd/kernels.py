@@ -626,6 +626,36 @@ def depthwise3x3_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
     return (y, mean) if want_mean else y
 
 
+def depthwise5x5_supported(H, W, pad):
+    """Whether K15 takes an [.., H, W] plane with padding `pad` (an int or (left, right, top, bottom)): the
+    padded plane is staged through LDS and may be at most 112 x 112 (csrc/depthwise5x5.hip)."""
+    pl, pr, pt, pb = (pad,) * 4 if isinstance(pad, int) else tuple(int(p) for p in pad)
+    return H + pt + pb <= 112 and W + pl + pr <= 112
+
+
+def depthwise5x5_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
+    """K15: y = act(depthwise_conv5x5(x, weight) + bias) in one pass (+ the [B, C] f32 mean of y over
+    H*W if want_mean).  x NCHW-contiguous f32 / f16 / bf16, weight [C, 1, 5, 5] or [C, 5, 5].
+    pad: one int (every side, 0..2) or (left, right, top, bottom) like torch.nn.ZeroPad2d (left / top 0..2,
+    right / bottom 0..3).  A function of its own beside depthwise3x3_bias_act: the 3x3 layers never pass here
+    and the 5x5 layers never pass there."""
+    require_cuda(x, weight, bias)
+    if not x.is_contiguous():
+        raise ValueError('depthwise5x5_bias_act needs an NCHW-contiguous tensor')
+    if weight.numel() != x.shape[1] * 25:
+        raise ValueError(f'depthwise5x5_bias_act needs a [C, 5, 5] weight, got {tuple(weight.shape)}')
+    B, C, H, W = x.shape
+    pl, pr, pt, pb = (pad,) * 4 if isinstance(pad, int) else tuple(int(p) for p in pad)
+    OH, OW = (H + pt + pb - 5) // stride + 1, (W + pl + pr - 5) // stride + 1
+    y = torch.empty(B, C, max(OH, 0), max(OW, 0), device=x.device, dtype=x.dtype)
+    mean = torch.empty(B, C, device=x.device, dtype=torch.float32) if want_mean else None
+    check(_lib.load().mtr_depthwise5x5_bias_act_padded(
+        _ptr(x), dtype_code(x.dtype), _ptr(weight.contiguous().float()), _ptr(bias.contiguous().float()),
+        ACT_CODES[act], B, C, H, W, int(stride), pt, pl, pb, pr, _ptr(y), None if mean is None else _ptr(mean),
+        current_stream_ptr(x.device)), 'mtr_depthwise5x5_bias_act_padded')
+    return (y, mean) if want_mean else y
+
+
 # K12: the squeeze-excite gate of an MBConv block (csrc/se.hip)
 
 SE_GATE_CODES = {'sigmoid': 0, 'hardsigmoid': 1}

@@ -11,6 +11,10 @@ the graph cache's replay counts are reported with each pair.  bench.py itself is
 --ab k14h compares the 16-bit copy with itself instead: A = Conv3x3BiasAct.use_k14h off (the dense 3x3 layers on MIOpen
 + K10), B = on (K14h); the same tree and weights, so the pairs isolate K14h.  The rows keep their field names
 (autocast_* = arm A, copy_* = arm B) and carry ab='k14h'.
+--ab k15 does the same for the depthwise 5x5 layers (MobileNetV3: --config 3, 64 boxes x 5 augmentations): both arms
+are folded from the same network, A with DepthwiseBiasAct.kernel_sizes = (3,) at fold time (the 5x5 layers as
+DepthwiseConv2d + K10, the tree from before K15), B with (3, 5) (K15); --dtype f32 compares the f32 copies, f16 /
+bf16 the 16-bit copies.  The rows carry ab='k15'.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -24,33 +28,44 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--config', type=int, default=1, choices=[1, 4])
+    ap.add_argument('--config', type=int, default=1, choices=[1, 3, 4])
     ap.add_argument('--pairs', type=int, default=5)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--dtype', choices=['f16', 'bf16'], default='f16')
+    ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h'], default='copy',
-                    help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on")
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15'], default='copy',
+                    help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
+                         "--dtype f32) folded without vs with K15")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
+    if (args.dtype == 'f32' or args.config == 3) and args.ab != 'k15':
+        ap.error('--dtype f32 and --config 3 go with --ab k15')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
     import bench
-    from metrabs_amd.backbones import Conv3x3BiasAct, fold_batchnorm
-    dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
+    from metrabs_amd.backbones import Conv3x3BiasAct, DepthwiseBiasAct, fold_batchnorm
+    dt = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': None}[args.dtype]
     argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype]
     bargs = bench.parse_args()
     sys.argv = argv
     dev = torch.device('cuda')
     est_a, _ = bench.build_model(bargs, dev)                     # f32 copy under 16-bit autocast
     est_b, _ = bench.build_model(bargs, dev)                     # the same seeded network ...
-    est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt)
-    est_b.crop_dtype = est_b.crop_model.input_dtype              # ... as its 16-bit copy
+    if dt is not None:
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_b.crop_dtype = est_b.crop_model.input_dtype          # ... as its 16-bit copy
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
+    if args.ab == 'k15':                                         # arm A: the same copy, folded as before K15
+        DepthwiseBiasAct.kernel_sizes = (3,)
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        DepthwiseBiasAct.kernel_sizes = (3, 5)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        assert not any(isinstance(m, DepthwiseBiasAct) and m.k == 5 for m in est_a.crop_model.backbone.modules())
+        assert any(isinstance(m, DepthwiseBiasAct) and m.k == 5 for m in est_b.crop_model.backbone.modules())
     est_f, _ = bench.build_model(bargs, dev)                     # f32 folded: the accuracy reference
     est_f.crop_model.autocast_dtype = None
     est_f.crop_dtype = torch.float32
@@ -59,7 +74,7 @@ def main():
     est_f.graph_batches = False
 
     g = torch.Generator().manual_seed(5)
-    n_box, frames, im_h, im_w = bargs.batch, bargs.frames, 1080, 1920
+    n_box, frames, im_h, im_w = bargs.batch // max(bargs.num_aug, 1), bargs.frames, 1080, 1920   # (boxes, each sampled num_aug times)
     images = torch.randint(0, 256, (frames, 3, im_h, im_w), dtype=torch.uint8, generator=g).to(dev)
     bw = 60 + 340 * torch.rand(n_box, generator=g)
     bh = 150 + 750 * torch.rand(n_box, generator=g)
@@ -74,7 +89,7 @@ def main():
     def call(est):
         # the class switch is read when a forward runs eagerly or is captured; a replayed graph keeps its arm
         Conv3x3BiasAct.use_k14h = not (args.ab == 'k14h' and est is est_a)
-        r = est.estimate_poses_batched(images, boxes, intrinsic_matrix=K, internal_batch_size=n_box,
+        r = est.estimate_poses_batched(images, boxes, intrinsic_matrix=K, internal_batch_size=bargs.batch,
                                        num_aug=bargs.num_aug)
         return torch.cat(r['poses3d'])
 
@@ -85,7 +100,7 @@ def main():
             call(est)
         ev[1].record()
         torch.cuda.synchronize()
-        return n_box * args.steps / (ev[0].elapsed_time(ev[1]) / 1e3)
+        return bargs.batch * args.steps / (ev[0].elapsed_time(ev[1]) / 1e3)
 
     rows = []
     with torch.inference_mode():

@@ -14,7 +14,10 @@ then one forward in which a forward pre-hook on every module first launches a ma
 (torch.cuda._sleep(0), `spin_kernel`).  The kernels between two markers belong to the module entered
 last; `report` names each kernel's role in its block (SE fc1 / bias / act, fc2, gate, mul, project,
 K10, K11, se_gate, ...) from that module and the kernel's name and writes a markdown table: per MBConv
-block the time of every role, the sum of the squeeze-excite tail, and per project shape the GEMM time.
+block the time of every role, the sum of the squeeze-excite tail, per project shape the GEMM time, and per
+depthwise layer (k, C, map, stride) its convolution kernel + K10, or K11 / K15 (`record --no-k15`: the 5x5
+layers folded as before K15).  The block tables are EfficientNetV2's; other backbones (`--backbone mobilenetv3
+--batch 320`: configs[3]) get the depthwise table and the split by kernel kind.
 Marker kernels and the gaps they open are not counted; kernel durations are the tracer's.
 `record --precision` picks the arithmetic: f32 (the default, as above), f16-autocast / bf16-autocast (the f32
 copy under torch.autocast, 16-bit crops: bench.py's --precision f16 / bf16), f16-copy / bf16-copy (the 16-bit
@@ -40,7 +43,10 @@ def record(args):
     import torch
     sys.path.insert(0, ROOT)
     import bench
-    from metrabs_amd.backbones import build_backbone, calibrate_batchnorm, fold_batchnorm
+    from metrabs_amd.backbones import (ConvBiasAct, DepthwiseBiasAct, DepthwiseConv2d, build_backbone,
+                                       calibrate_batchnorm, fold_batchnorm)
+    if args.no_k15:   # the module tree from before K15: 5x5 depthwise layers as DepthwiseConv2d + K10
+        DepthwiseBiasAct.kernel_sizes = (3,)
     dev = torch.device('cuda')
     torch.manual_seed(1234)
     dt = {'f32': None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.precision.split('-')[0]]
@@ -60,10 +66,14 @@ def record(args):
             else contextlib.nullcontext)
     order = []
 
+    depthwise, dw_maps = {}, {}
+
     def hook(name):
         def pre(mod, inp):
             torch.cuda._sleep(0)
             order.append(name)
+            if inp and hasattr(inp[0], 'shape') and inp[0].dim() == 4:
+                dw_maps[name] = f'{inp[0].shape[2]}x{inp[0].shape[3]}'
         return pre
 
     with torch.inference_mode():
@@ -78,12 +88,17 @@ def record(args):
         for h in handles:
             h.remove()
     shapes = {}
+    for n, m in net.named_modules():  # depthwise layers for the report: kernel size, channels, input map, stride
+        if isinstance(m, DepthwiseBiasAct):
+            depthwise[n] = [m.k, m.weight.shape[0], dw_maps.get(n), m.stride]
+        elif isinstance(m, ConvBiasAct) and isinstance(m.conv, DepthwiseConv2d):
+            depthwise[n] = [m.conv.kernel_size[0], m.conv.in_channels, dw_maps.get(n), m.conv.stride[0]]
     for n, m in net.named_modules():  # 1x1 conv shapes for the report
         if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (1, 1) and m.groups == 1:
             shapes[n] = [m.in_channels, m.out_channels]
     os.makedirs(os.path.dirname(os.path.abspath(args.markers)), exist_ok=True)
     with open(args.markers, 'w') as f:
-        json.dump(dict(order=order, conv1x1=shapes, batch=args.batch, res=args.res,
+        json.dump(dict(order=order, conv1x1=shapes, depthwise=depthwise, batch=args.batch, res=args.res,
                        feature_shape=list(feat.shape), precision=args.precision, backbone=args.backbone), f)
     print(f'recorded {len(order)} markers')
 
@@ -115,8 +130,12 @@ def _kind(kname):
         return 'K13'
     if 'bias_act' in k:
         return 'K10'
-    if 'depthwise' in k:
+    if 'depthwise5x5' in k:
+        return 'K15'
+    if 'depthwise3x3' in k:
         return 'K11'
+    if 'depthwise' in k:  # PyTorch's own depthwise kernel (conv_depthwise2d_forward_kernel)
+        return 'dw conv'
     if k.startswith('cijk') or 'gemm' in k:
         return 'gemm'
     if 'sigmoid' in k:
@@ -193,6 +212,32 @@ def _fused_table(per_kernel, pat):
     return lines
 
 
+def _depthwise_table(per_kernel, depthwise, total):
+    """Every depthwise layer: k, C, input map, stride, then what served it -- PyTorch's depthwise kernel (or MIOpen)
+    + K10, or the one-pass K11 / K15."""
+    if not depthwise:
+        return []
+    cols = ['conv', 'K10', 'K11', 'K15', 'other']
+    rows = OrderedDict((n, defaultdict(float)) for n in depthwise)
+    for module, kind, kname, us in per_kernel:
+        for n in depthwise:
+            if module == n or module.startswith(n + '.'):
+                col = kind if kind in ('K10', 'K11', 'K15') else 'conv' if kind in ('dw conv', 'conv') else 'other'
+                rows[n][col] += us
+                break
+    lines = ['', '## Depthwise layers', '',
+             '| layer | k | C | map | stride | ' + ' | '.join(cols) + ' | **sum** |', '|---|---|---|---|---|' + '---|' * (len(cols) + 1)]
+    by_k = defaultdict(float)
+    for n, b in rows.items():
+        k, C, hw, stride = depthwise[n]
+        t = sum(b.values())
+        by_k[k] += t
+        lines.append(f'| {n} | {k} | {C} | {hw} | {stride} | ' + ' | '.join(f'{b[c]:.1f}' for c in cols) + f' | **{t:.1f}** |')
+    lines += ['', ' '.join(f'{k}x{k} layers: **{v:.1f} us** ({100 * v / total:.1f} % of the forward\'s {total:.1f} us).'
+                           for k, v in sorted(by_k.items()))]
+    return lines
+
+
 def report(args):
     meta = json.load(open(args.markers))
     order = meta['order']
@@ -262,6 +307,11 @@ def report(args):
     for shape, v in sorted(proj.items()):
         lines.append(f'| {" -> ".join(map(str, shape))} | {len(v)} | {sum(v) / len(v):.1f} | {sum(v):.1f} |')
     lines += fused
+    if not blocks:   # not an EfficientNetV2 module tree: the block tables above are empty
+        lines = lines[:4] + [f'One marked forward (tools/backbone_trace.py): {len(per_kernel)} kernels, {total:.1f} us of '
+                             f'kernel time (markers excluded).  Times in us.  (The per-block tables are written for '
+                             f'EfficientNetV2 and left out for this backbone.)']
+    lines += _depthwise_table(per_kernel, meta.get('depthwise', {}), total)
     kinds = defaultdict(float)
     for _, kind, _, us in per_kernel:
         kinds[kind] += us
@@ -281,6 +331,8 @@ def main():
     r.add_argument('--res', type=int, default=256)
     r.add_argument('--warmup', type=int, default=3)
     r.add_argument('--backbone', default='effnetv2-s')
+    r.add_argument('--no-k15', action='store_true',
+                   help='fold with DepthwiseBiasAct.kernel_sizes = (3,): 5x5 depthwise layers on DepthwiseConv2d + K10')
     r.add_argument('--precision', default='f32',
                    choices=['f32', 'f16-autocast', 'bf16-autocast', 'f16-copy', 'bf16-copy'])
     p = sub.add_parser('report')

@@ -269,11 +269,47 @@ def bench_depthwise():
     return out
 
 
+def bench_depthwise5x5():
+    """K15: depthwise 5x5 + bias + activation (+ plane mean) in one pass at MobileNetV3-Large's shapes (read x +
+    write y = the algorithmic bytes), beside PyTorch's depthwise kernel + the elementwise ops.  (Cache-hot like the
+    other cases here; tools/depthwise_ab.py times the layers on buffers rotating through HBM.)"""
+    import torch.nn.functional as F
+    out = []
+    g = torch.Generator(device='cuda').manual_seed(0)
+    for name, (B, C, H), stride, act, dt in [('B=320 72ch 64x64 s2 relu f32', (320, 72, 64), 2, 'relu', torch.float32),
+                                             ('B=320 120ch 32x32 s1 relu f32', (320, 120, 32), 1, 'relu', torch.float32),
+                                             ('B=320 672ch 16x16 s2 hardswish f32', (320, 672, 16), 2, 'hardswish', torch.float32),
+                                             ('B=320 960ch 8x8 s1 hardswish f32', (320, 960, 8), 1, 'hardswish', torch.float32),
+                                             ('B=320 960ch 8x8 s1 hardswish f16', (320, 960, 8), 1, 'hardswish', torch.float16)]:
+        x = torch.randn(B, C, H, H, device='cuda', generator=g).to(dt)
+        w = torch.randn(C, 1, 5, 5, device='cuda', generator=g) * 0.2
+        b = torch.randn(C, device='cuda', generator=g)
+        t = timeit(lambda: kernels.depthwise5x5_bias_act(x, w, b, act, stride, 2, want_mean=True))
+        wd, bd = w.to(dt), b.to(dt)
+        fn = F.relu if act == 'relu' else F.hardswish
+
+        def torch_path():
+            prev = torch.backends.cudnn.enabled
+            torch.backends.cudnn.enabled = False
+            try:
+                y = fn(F.conv2d(x, wd, bd, stride, 2, groups=C))
+            finally:
+                torch.backends.cudnn.enabled = prev
+            return y, y.mean((2, 3))
+        tt = timeit(torch_path)
+        oh = (H + 4 - 5) // stride + 1
+        nbytes = (x.numel() + B * C * oh * oh) * x.element_size()
+        out.append(dict(kernel='depthwise5x5', case=name, us=round(t * 1e6, 1), torch_ops_us=round(tt * 1e6, 1),
+                        GBps=round(nbytes / t / 1e9, 1), frac_hbm=round(nbytes / t / HBM, 3)))
+    return out
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['decode', 'head', 'warp', 'recon', 'detector', 'filter', 'bias_act', 'depthwise']
+    which = sys.argv[1:] or ['decode', 'head', 'warp', 'recon', 'detector', 'filter', 'bias_act', 'depthwise',
+                             'depthwise5x5']
     benches = [('decode', bench_decode), ('head', bench_head), ('warp', bench_warp_pyramid),
                ('recon', bench_recon), ('detector', bench_detector_pre), ('filter', bench_filter),
-               ('bias_act', bench_bias_act), ('depthwise', bench_depthwise)]
+               ('bias_act', bench_bias_act), ('depthwise', bench_depthwise), ('depthwise5x5', bench_depthwise5x5)]
     for name, fn in benches:
         if name in which or (name == 'warp' and 'pyramid' in which):
             for r in fn():
