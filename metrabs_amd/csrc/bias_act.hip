@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void bias_act_rowmean_kernel(T* __restrict__ y
     Pack p = *reinterpret_cast<const Pack*>(base + (long long)v * VEC);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      const float a = activate<ACT>(to_f32(p.v[e]) + b);
+      const float a = settled(activate<ACT>(to_f32(p.v[e]) + b));
       if constexpr (sizeof(T) == 4) p.v[e] = a; else p.v[e] = T(a);
       sum += to_f32(p.v[e]);
     }

@@ -77,6 +77,19 @@ __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(__half v) { return __half2float(v); }
 __device__ __forceinline__ float to_f32(__hip_bfloat16 v) { return __bfloat162float(v); }
 
+// The f32 result an epilogue is about to round to the tensor's dtype, store, and add to a row / plane mean, made
+// opaque to the optimiser (no instruction): the means of K10 and K11 are means of the STORED values.  Left to itself
+// the compiler fuses the activation's last product (silu, hardswish) into whatever follows, per use and per
+// instantiation: for f32 tensors into the mean's addition (an fma of the unrounded product -- except where the SLP
+// vectoriser had packed the products: K11's vector-row and scalar-row kernels gave means that differed in the last
+// bit), for f16 tensors into the conversion of the copy that is summed (v_fma_mixlo_f16, one rounding) but not of the
+// copy that is stored (v_mul_f32 + v_cvt_pk_f16_f32, two roundings), so the mean was off by an f16 ulp of one element
+// where the two disagree.
+__device__ __forceinline__ float settled(float a) {
+  asm("" : "+v"(a));
+  return a;
+}
+
 // VEC consecutive elements -> fp32 registers.  16-byte loads for f32x4, 8-byte for f16x4/bf16x4.
 template <typename T, int VEC>
 __device__ __forceinline__ void load_vec(const T* __restrict__ p, float (&out)[VEC]) {

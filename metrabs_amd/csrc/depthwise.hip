@@ -133,7 +133,7 @@ __device__ __forceinline__ float dw_finish(T* __restrict__ y, const DwGeom& g, i
   float sum = 0.0f;
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
-    const float a = activate<ACT>(acc[o] + r.b);
+    const float a = settled(activate<ACT>(acc[o] + r.b));
     if constexpr (sizeof(T) == 4) out.v[o] = a; else out.v[o] = T(a);
     sum += to_f32(out.v[o]);
   }
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void depthwise3x3_s1_block_kernel(
     V4 out;
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const float a = activate<ACT>(acc[o]);
+      const float a = settled(activate<ACT>(acc[o]));
       if constexpr (sizeof(T) == 4) out.v[o] = a; else out.v[o] = T(a);
       sum += to_f32(out.v[o]);
     }

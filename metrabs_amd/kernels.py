@@ -614,6 +614,8 @@ def depthwise3x3_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
     require_cuda(x, weight, bias)
     if not x.is_contiguous():
         raise ValueError('depthwise3x3_bias_act needs an NCHW-contiguous tensor')
+    if weight.numel() != x.shape[1] * 9:
+        raise ValueError(f'depthwise3x3_bias_act needs a [C, 3, 3] weight, got {tuple(weight.shape)}')
     B, C, H, W = x.shape
     pl, pr, pt, pb = (pad,) * 4 if isinstance(pad, int) else tuple(int(p) for p in pad)
     OH, OW = (H + pt + pb - 3) // stride + 1, (W + pl + pr - 3) // stride + 1
