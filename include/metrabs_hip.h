@@ -524,6 +524,19 @@ int mtr_se_gate(const float* mean /*[B*C]*/, const float* w1, const float* b1, c
                 const float* b2, int act, int gate_fn, int B, int C, int S, float* gate /*[B*C]*/,
                 mtr_stream_t stream);
 
+/* mtr_se_gate with the layout of w2 and the kernel configuration stated.  w2_layout: MTR_SE_W2_CS is
+ * w2 [C, S] as above, MTR_SE_W2_SC its transpose [S, C] (made once from the constant weight of an inference
+ * copy: the fc2 loads of a wave are then contiguous).  config: -1 the library's own choice (what mtr_se_gate
+ * takes), 0 .. 3 a (images per workgroup, channels per workgroup) split of (4, 256), (4, 1024), (8, 256),
+ * (2, 512); one that does not fit the shape (more than 65535 image groups, more than 160 KiB of LDS) returns
+ * MTR_E_SHAPE.  An image's gate has the same bits for every layout, configuration and B.  Other values of
+ * either argument: MTR_E_PARAM; else the rules of mtr_se_gate. */
+#define MTR_SE_W2_CS 0
+#define MTR_SE_W2_SC 1
+int mtr_se_gate_opts(const float* mean /*[B*C]*/, const float* w1, const float* b1, const float* w2,
+                     const float* b2, int act, int gate_fn, int B, int C, int S, float* gate /*[B*C]*/,
+                     mtr_stream_t stream, int w2_layout, int config);
+
 /* K13 (outside the reference's hot path, like K10): a 1x1 stride-1 unpadded convolution of the backbone's
  * inference copy as one f32 MFMA GEMM with the K10 epilogue and the squeeze-excite gate folded in:
  *   y[b, m, p] = act(bias[m] + sum_k weight[m, k] * (x[b, k, p] * gate[b, k])) (+ residual[b, m, p])
@@ -535,6 +548,18 @@ int mtr_se_gate(const float* mean /*[B*C]*/, const float* w1, const float* b1, c
 int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weight, const float* bias,
                          const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
                          int M, int K, int HW, void* y, mtr_stream_t stream);
+
+/* mtr_conv1x1_bias_act with the tile configuration stated (tests, A/B runs).  config: -1 the library's own choice
+ * (what mtr_conv1x1_bias_act takes, a pure function of (M, K, HW, B)), 0 wide (192 x 128), 1 square (128 x 128),
+ * 2 tall (32 w x 32), 3 deep-K (32 w x 16, three k-tiles of 32 in flight); else MTR_E_PARAM.  Every configuration
+ * takes every shape and returns the same bits. */
+int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* weight, const float* bias,
+                              const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
+                              int M, int K, int HW, void* y, mtr_stream_t stream, int config);
+
+/* Host only: what `config` (as above) resolves to for a shape.  plan[0 .. 3] = configuration (0 .. 3), waves along
+ * the channels, channels per workgroup, columns per workgroup. */
+int mtr_conv1x1_plan(int M, int K, int HW, long long B, int config, int* plan /*[4]*/);
 
 /* K13h (outside the reference's hot path, like K10): mtr_conv1x1_bias_act for f16 / bf16 tensors, one 16-bit
  * MFMA GEMM (v_mfma_f32_32x32x16_{f16,bf16}) with the K10 epilogue and the squeeze-excite gate folded in:

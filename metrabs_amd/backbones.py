@@ -83,7 +83,7 @@ class SqueezeExcite(nn.Module):
             # fc1, + b1, act, fc2, + b2, gate as ONE HIP launch from the f32 mean (K12)
             from . import kernels
             g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
-                                _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)])
+                                _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)], w2t=self._fc2_wt())
             for dst in self.gate_to:
                 if dst.k13_takes(x) or dst.k13h_takes(x):
                     # the project conv (K13 / K13h) multiplies x by the gate as it stages x: no x * g pass
@@ -103,6 +103,17 @@ class SqueezeExcite(nn.Module):
         s = mean.view(x.shape[0], x.shape[1], 1, 1) if mean is not None else \
             x.mean((2, 3), keepdim=True, dtype=self.fc1.weight.dtype)
         return x * self.gate(self.fc2(self.act(self.fc1(s)))).to(x.dtype)
+
+    _w2t = None
+
+    def _fc2_wt(self):
+        """fc2's weight transposed to [S, C] for K12 (a wave's fc2 loads are then contiguous): made on the first
+        fused forward and again whenever the weight has moved or been written since (not part of the state dict)."""
+        w = self.fc2.weight
+        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
+        if self._w2t is None or self._w2t[0] != key:
+            self._w2t = (key, w.detach().reshape(w.shape[0], -1).t().contiguous())
+        return self._w2t[1]
 
     def _fused_gate_ok(self):
         """K12 computes no gradient: only where none is wanted, for the layer types it implements."""
@@ -308,8 +319,8 @@ class ConvBiasAct(nn.Module):
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
     use_k13 = True
     # (Cin, Cout, H * W) where K13 measured slower than rocBLAS + K10 (+ x * gate) at the bench shape
-    # (EfficientNetV2-S, batch 64, 256 px): these stay on the library path
-    k13_slower = frozenset({(960, 256, 64), (1536, 256, 64), (256, 1280, 64)})
+    # (EfficientNetV2-S, batch 64, 256 px; DESIGN.md sections 11 and 15): these stay on the library path
+    k13_slower = frozenset({(1536, 256, 64)})
 
     def k13_takes(self, x):
         """Whether forward(x) runs on K13 (conv1x1.hip): a 1x1 stride-1 unpadded ungrouped conv on an f32

@@ -22,6 +22,8 @@
 // past B * HW and k past K are zero-filled, never stored.  The configuration is a pure function of
 // (M, K, HW, B) (pick_config); the k order is 0, 1, 2, ... in every configuration, so the result does
 // not depend on it.  No atomics, no split-K: the same inputs give the same bits.
+#include <type_traits>
+
 #include "common.h"
 
 namespace mtr {
@@ -166,6 +168,181 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
   }
 }
 
+// The deep-K configuration: few output channels behind a long k loop (the project convolutions of the
+// last stages: 8x8 maps, K = 960 .. 1536).  The tall tiles above run those with ONE wave per SIMD, one
+// k-tile of global loads in flight and a wait + LDS write + barrier behind every tile's MFMAs that no
+// other wave covers.  Here a workgroup of WAVES waves takes 32 WAVES channels (all of M = 256 with 8
+// waves: x is read once) x 16 columns on v_mfma_f32_16x16x4_f32 (the same k-ordered fmaf chain per
+// output as the 32x32x2 form, so the same bits), which gives twice the waves of a 32-column tile: two
+// per SIMD, one's staging under the other's MFMAs.  k-tiles of 32 go global -> registers -> a ring of
+// three LDS stages: tile t + 3 is requested before tile t is multiplied and tile t + 2 (requested one
+// whole tile earlier) is written to LDS between the two halves of tile t's MFMAs, so a load has two
+// tiles of MFMA time to arrive and the barrier follows MFMAs, not LDS writes.  W is staged as it lies in
+// memory ([m][k], 16-byte LDS writes, rows 36 floats apart: the fragment reads of 16 rows x 4 k hit
+// distinct banks), x as [k][16].
+constexpr int kDkBK = 32, kDkBN = 16, kDkStages = 3;
+constexpr int kDkLDW = kDkBK + 4;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t deepk_lds_bytes(int waves) {
+  return (size_t)kDkStages * (kDkBK * kDkBN + 32 * waves * kDkLDW) * sizeof(float);
+}
+
+template <int WAVES, int ACT>
+__global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ gate, const float* __restrict__ residual, float* __restrict__ y, int M,
+    int K, int HW, int n_total, FastDiv by_hw) {
+  constexpr int NT = 64 * WAVES, BM = 32 * WAVES;
+  constexpr int XS = kDkBK * kDkBN, WS = BM * kDkLDW;  // floats per stage
+  static_assert(BM * (kDkBK / 4) == 4 * NT, "W loader mapping");
+  extern __shared__ float4 dk_lds[];
+  float* xs = reinterpret_cast<float*>(dk_lds);  // [stage][k][16]
+  float* ws = xs + kDkStages * XS;               // [stage][m][kDkLDW]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * kDkBN;
+  const long long khw = (long long)K * HW;
+
+  // x: every thread one k row and XV consecutive columns of the 32 x 16 tile, fixed for the whole k loop
+  constexpr int XV = XS / NT;  // 1 (8 waves) or 2 (4 waves)
+  static_assert(XV * NT == XS && (XV == 1 || XV == 2), "x loader mapping");
+  const int xp = (tid % (kDkBN / XV)) * XV, xk = tid / (kDkBN / XV);
+  const int xcol = n0 + xp;
+  const bool xcol_ok = xcol < n_total;
+  const unsigned xb = xcol_ok ? fastdiv((unsigned)xcol, by_hw) : 0u;
+  const float* xsrc = xcol_ok ? x + (long long)xb * khw + (xcol - (int)xb * HW) : x;
+  const bool has_gate = gate != nullptr;
+  const float* gsrc = has_gate ? gate + (long long)xb * K : x;  // (no gate: any K readable floats, multiplied by 1)
+  // W: every thread four 16-byte groups, rows NT / 8 apart
+  const int wk4 = tid & 7, wr0 = tid >> 3;
+
+  // Loads carry no condition and no arithmetic, and every thread issues the same ones: a group past M, K or
+  // B * HW is read from a clamped address and zeroed (and x multiplied by its gate) on its way to LDS, two
+  // tiles later.  A select or a product beside the load makes the loop wait for it at once; a branch around
+  // it makes the compiler wait for the loads of the tile before at the next load.
+  // Two register sets (tiles t + 2 and t + 3 are in flight together), always indexed by a constant.
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 rw[2][4] = {{zero, zero, zero, zero}, {zero, zero, zero, zero}};
+  float rx[2][XV] = {}, rg[2] = {1.0f, 1.0f};
+  auto load_tile = [&](int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * kDkBK;
+    const int kx = min(k0 + xk, K - 1);
+    if constexpr (XV == 2) {
+      const float2 t = *reinterpret_cast<const float2*>(xsrc + (long long)kx * HW);
+      rx[P][0] = t.x; rx[P][XV - 1] = t.y;
+    } else {
+      rx[P][0] = xsrc[(long long)kx * HW];
+    }
+    rg[P] = gsrc[kx];
+    const int k = min(k0 + wk4 * 4, K - 4);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int m = min(m0 + wr0 + v * (NT / 8), M - 1);
+      rw[P][v] = *reinterpret_cast<const float4*>(w + (long long)m * K + k);
+    }
+  };
+  auto store_tile = [&](int stage, int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * kDkBK;
+    const float g = has_gate ? rg[P] : 1.0f;  // the squeeze-excite gate, once per staged element: x * g rounded as torch does
+    const bool x_ok = xcol_ok && k0 + xk < K;
+    float* xd = &xs[stage * XS + xk * kDkBN + xp];
+    if constexpr (XV == 2) {
+      *reinterpret_cast<float2*>(xd) = make_float2(x_ok ? rx[P][0] * g : 0.0f, x_ok ? rx[P][XV - 1] * g : 0.0f);
+    } else {
+      *xd = x_ok ? rx[P][0] * g : 0.0f;
+    }
+    const bool k_ok = k0 + wk4 * 4 < K;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int row = wr0 + v * (NT / 8);
+      const bool ok = k_ok && m0 + row < M;  // (selects of scalars: a select of two float4 objects goes through memory)
+      float4 u = rw[P][v];
+      u.x = ok ? u.x : 0.0f; u.y = ok ? u.y : 0.0f; u.z = ok ? u.z : 0.0f; u.w = ok ? u.w : 0.0f;
+      *reinterpret_cast<float4*>(&ws[stage * WS + row * kDkLDW + wk4 * 4]) = u;
+    }
+  };
+
+  f32x4 acc[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[f][r] = 0.0f;
+
+  // lane = (column or channel c of the 16, k group kg of the 4)
+  const int c = lane & 15, kg = lane >> 4;
+  auto multiply = [&](int stage, int kk0) {
+    const float* xb_ = &xs[stage * XS + kg * kDkBN + c];
+    const float* wb_ = &ws[stage * WS + (wave * 32 + c) * kDkLDW + kg];
+#pragma unroll
+    for (int kk = kk0; kk < kk0 + kDkBK / 2; kk += 4) {
+      const float a = xb_[kk * kDkBN];
+      const float b0 = wb_[kk], b1 = wb_[16 * kDkLDW + kk];
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[1], 0, 0, 0);
+    }
+  };
+
+  const int n_tiles = (K + kDkBK - 1) / kDkBK;
+  constexpr std::integral_constant<int, 0> ra{};
+  constexpr std::integral_constant<int, 1> rb{};
+  load_tile(0, ra);
+  if (n_tiles > 1) load_tile(1, rb);
+  store_tile(0, 0, ra);
+  if (n_tiles > 1) store_tile(1, 1, rb);
+  if (n_tiles > 2) load_tile(2, ra);
+  __syncthreads();
+  // at the top of step t: tiles t and t + 1 are in LDS, tile t + 2 is on its way to `hold`
+  int stage = 0;
+  auto step = [&](int t, auto hold, auto issue, auto guarded) {
+    constexpr bool G = decltype(guarded)::value;
+    if (!G || t + 3 < n_tiles) load_tile(t + 3, issue);
+    multiply(stage, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // stage of tile t + 2 = stage of tile t - 1: last read before the previous barrier
+    if (!G || t + 2 < n_tiles) store_tile(stage == 0 ? 2 : stage - 1, t + 2, hold);
+    __builtin_amdgcn_sched_barrier(0);
+    multiply(stage, kDkBK / 2);
+    stage = stage == 2 ? 0 : stage + 1;
+    __syncthreads();
+  };
+  // the body of the loop has no condition (see load_tile); the last steps, which have, run apart
+  int t = 0;
+  for (; t + 4 < n_tiles; t += 2) {
+    step(t, ra, rb, std::false_type{});
+    step(t + 1, rb, ra, std::false_type{});
+  }
+  for (; t < n_tiles; t += 2) {
+    step(t, ra, rb, std::true_type{});
+    if (t + 1 < n_tiles) step(t + 1, rb, ra, std::true_type{});
+  }
+
+  // epilogue: lane holds channel .. + c, positions 4 kg + 0..3 of the 16 columns
+  const int col = n0 + 4 * kg;
+  if (col >= n_total) return;
+  const unsigned b = fastdiv((unsigned)col, by_hw);
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int m = m0 + wave * 32 + f * 16 + c;
+    if (m >= M) continue;
+    const float bm = bias[m];
+    const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
+    float4 r;
+    r.x = activate<ACT>(acc[f][0] + bm);
+    r.y = activate<ACT>(acc[f][1] + bm);
+    r.z = activate<ACT>(acc[f][2] + bm);
+    r.w = activate<ACT>(acc[f][3] + bm);
+    if (residual) {  // the block's skip connection, added after the activation (K10's order)
+      const float4 q = *reinterpret_cast<const float4*>(residual + off);
+      r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+    }
+    *reinterpret_cast<float4*>(y + off) = r;
+  }
+}
+
 // The tile table.  Chosen from the shape only; see DESIGN.md section 11 for the measurements.
 //   wide  (WM 2, WN 2, FM 3, FN 2): 192 x 128 -- many output channels (expand), when it still gives
 //                                    >= 512 workgroups
@@ -175,20 +352,46 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
 //                                    at w = 4 (one wave per SIMD: half the barriers per MFMA), BK 16
 //                                    elsewhere (at w = 5 the BK-32 tiles take 58 KB of LDS, one
 //                                    workgroup per CU, 25 % slower)
-enum Conv1x1Config { kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2 };
+//   deepk (WAVES w, 32 w x 16, k-tiles of 32 in a ring of three): few output channels behind a long k
+//                                    loop (conv1x1_deepk_kernel above), w = 4 or 8
+enum Conv1x1Config { kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2, kCfgDeepK = 3, kCfgCount = 4 };
 
 struct Conv1x1Plan { int cfg, waves_m, bm, bn; };
+
+inline Conv1x1Plan plan_tall(int M) {
+  const int w = M <= 160 ? (M + 31) / 32 : 4;  // more than 160 channels: rows of 128-channel workgroups
+  return {kCfgTall, w, 32 * w, 32};
+}
+inline Conv1x1Plan plan_deepk(int M) {
+  const int w = M <= 128 ? 4 : 8;
+  return {kCfgDeepK, w, 32 * w, kDkBN};
+}
 
 inline Conv1x1Plan pick_config(int M, int K, int HW, long long B) {
   const long long n_total = B * HW;
   const long long n_tiles128 = (n_total + 127) / 128;
-  if (M <= 160) {
-    const int w = (M + 31) / 32;
-    return {kCfgTall, w, 32 * w, 32};
-  }
-  if (M == 256 && K >= 512) return {kCfgTall, 4, 128, 32};  // project at 8x8: two workgroups per 32 columns
+  if (M <= 160) return plan_tall(M);
+  // project at 8x8: deep-K (960 -> 256: 30.4 us against 35.3, 1536 -> 256: 48.6 against 61.6 at batch 64); larger
+  // maps keep two workgroups per 32 columns
+  if (M == 256 && K >= 512) return HW <= 64 ? plan_deepk(M) : plan_tall(M);
+  // many output channels over a short k loop and few columns (256 -> 1536 and the 256 -> 1280 head at 8x8, batch
+  // 64): 128 x 128 tiles give 1.5 rounds of workgroups on 256 CUs, 128 x 32 tiles twelve even ones (40.4 us against
+  // 48.0, 38.9 against 47.0)
+  if (M >= 1024 && M % 128 == 0 && K <= 256 && n_tiles128 <= 32) return plan_tall(M);
   if (M % 192 == 0 && (M / 192) * n_tiles128 >= 512) return {kCfgWide, 2, 192, 128};
   return {kCfgSquare, 2, 128, 128};
+}
+
+// config: -1 the library's own choice, else a Conv1x1Config forced on the shape (every one takes every shape)
+inline int plan_for(int M, int K, int HW, long long B, int config, Conv1x1Plan* p) {
+  switch (config) {
+    case -1: *p = pick_config(M, K, HW, B); return MTR_OK;
+    case kCfgWide: *p = {kCfgWide, 2, 192, 128}; return MTR_OK;
+    case kCfgSquare: *p = {kCfgSquare, 2, 128, 128}; return MTR_OK;
+    case kCfgTall: *p = plan_tall(M); return MTR_OK;
+    case kCfgDeepK: *p = plan_deepk(M); return MTR_OK;
+    default: return MTR_E_PARAM;
+  }
 }
 
 template <int WM, int WN, int FM, int FN, int BK>
@@ -216,11 +419,59 @@ static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias,
   return MTR_OK;
 }
 
+template <int WAVES>
+static int launch_conv1x1_deepk(const float* x, const float* w, const float* bias, const float* gate,
+                                const float* residual, float* y, int act, int M, int K, int HW,
+                                long long n_total, hipStream_t stream) {
+  constexpr int BM = 32 * WAVES;
+  constexpr size_t lds = deepk_lds_bytes(WAVES);
+  const long long gx = (n_total + kDkBN - 1) / kDkBN, gy = (M + BM - 1) / BM;
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WAVES);
+  const FastDiv by_hw = make_fastdiv((unsigned)HW);
+#define MTR_DK_LAUNCH(ACT)                                                                                 \
+  do {                                                                                                     \
+    if (lds > 64 * 1024) {                                                                                 \
+      const int e = allow_dynamic_lds((const void*)conv1x1_deepk_kernel<WAVES, ACT>, lds);                 \
+      if (e != MTR_OK) return e;                                                                           \
+    }                                                                                                      \
+    MTR_CLEAR_STALE();                                                                                     \
+    hipLaunchKernelGGL((conv1x1_deepk_kernel<WAVES, ACT>), grid, block, lds, stream, x, w, bias, gate,     \
+                       residual, y, M, K, HW, (int)n_total, by_hw);                                        \
+  } while (0)
+  switch (act) {
+    case kActNone: MTR_DK_LAUNCH(kActNone); break;
+    case kActRelu: MTR_DK_LAUNCH(kActRelu); break;
+    case kActSilu: MTR_DK_LAUNCH(kActSilu); break;
+    case kActHardswish: MTR_DK_LAUNCH(kActHardswish); break;
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_DK_LAUNCH
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
 }  // namespace mtr
+
+extern "C" int mtr_conv1x1_plan(int M, int K, int HW, long long B, int config, int* plan) {
+  if (!plan) return MTR_E_NULL;
+  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
+  mtr::Conv1x1Plan p;
+  const int e = mtr::plan_for(M, K, HW, B, config, &p);
+  if (e != MTR_OK) return e;
+  plan[0] = p.cfg; plan[1] = p.waves_m; plan[2] = p.bm; plan[3] = p.bn;
+  return MTR_OK;
+}
 
 extern "C" int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weight, const float* bias,
                                     const float* gate, const void* residual, int act, long long B, int M,
                                     int K, int HW, void* y, mtr_stream_t stream) {
+  return mtr_conv1x1_bias_act_opts(x, dtype, weight, bias, gate, residual, act, B, M, K, HW, y, stream, -1);
+}
+
+extern "C" int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* weight, const float* bias,
+                                         const float* gate, const void* residual, int act, long long B,
+                                         int M, int K, int HW, void* y, mtr_stream_t stream, int config) {
   if (!x || !weight || !bias || !y) return MTR_E_NULL;
   if (dtype != MTR_F32) return MTR_E_DTYPE;
   if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
@@ -238,12 +489,18 @@ extern "C" int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weigh
   float* yf = (float*)y;
   const long long n_total = B * HW;
   hipStream_t s = (hipStream_t)stream;
-  const mtr::Conv1x1Plan p = mtr::pick_config(M, K, HW, B);
+  mtr::Conv1x1Plan p;
+  if (mtr::plan_for(M, K, HW, B, config, &p) != MTR_OK) return MTR_E_PARAM;
   switch (p.cfg) {
     case mtr::kCfgWide:
       return mtr::launch_conv1x1_cfg<2, 2, 3, 2, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
     case mtr::kCfgSquare:
       return mtr::launch_conv1x1_cfg<2, 2, 2, 2, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+    case mtr::kCfgDeepK:
+      switch (p.waves_m) {
+        case 4: return mtr::launch_conv1x1_deepk<4>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+        default: return mtr::launch_conv1x1_deepk<8>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+      }
     default:
       switch (p.waves_m) {
         case 1: return mtr::launch_conv1x1_cfg<1, 1, 1, 1, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);

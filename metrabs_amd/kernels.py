@@ -663,22 +663,29 @@ def depthwise5x5_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
 SE_GATE_CODES = {'sigmoid': 0, 'hardsigmoid': 1}
 
 
-def se_gate(mean, w1, b1, w2, b2, act, gate_fn, out=None):
+def se_gate(mean, w1, b1, w2, b2, act, gate_fn, out=None, w2t=None, config=-1):
     """gate [B, C] f32 = gate_fn(w2 . act(w1 . mean + b1) + b2) in one launch: the squeeze-excite block
     of an MBConv from the [B, C] f32 channel mean K10 / K11 emit (instead of PyTorch-ROCm's fc1 GEMM,
     bias, activation, fc2 GEMM, bias and gate kernels).  w1 [S, C] (or the [S, C, 1, 1] conv weight),
-    w2 [C, S], b1 [S], b2 [C]; all f32.  act: a key of ACT_CODES, gate_fn: 'sigmoid' / 'hardsigmoid'."""
-    require_cuda(mean, w1, b1, w2, b2)
+    w2 [C, S], b1 [S], b2 [C]; all f32.  act: a key of ACT_CODES, gate_fn: 'sigmoid' / 'hardsigmoid'.
+    w2t: w2 transposed to [S, C] f32 contiguous (made once from a constant weight), read in place of w2 with
+    contiguous loads: the same bits.  config: -1 the library's choice, 0 .. 3 a forced workgroup split."""
+    require_cuda(mean, w1, b1, w2, b2, w2t)
     B, C = mean.shape[0], mean.shape[1]
     S = w1.shape[0]
     w1, w2 = w1.reshape(S, -1), w2.reshape(C, -1)
     if mean.dtype != torch.float32 or mean.numel() != B * C or w1.shape[1] != C or w2.shape[1] != S:
         raise ValueError('se_gate: mean [B, C] f32, w1 [S, C], w2 [C, S]')
+    if w2t is not None:
+        if w2t.shape != (S, C) or w2t.dtype != torch.float32 or not w2t.is_contiguous():
+            raise ValueError('se_gate: w2t must be [S, C] f32, contiguous')
+        w2 = w2t
     tensors = [t.contiguous().float() for t in (mean, w1, b1, w2, b2)]
     if out is None:
         out = torch.empty(B, C, device=mean.device, dtype=torch.float32)
-    check(_lib.load().mtr_se_gate(*(_ptr(t) for t in tensors), ACT_CODES[act], SE_GATE_CODES[gate_fn], B, C, S,
-                                  _ptr(out), current_stream_ptr(mean.device)), 'mtr_se_gate')
+    check(_lib.load().mtr_se_gate_opts(*(_ptr(t) for t in tensors), ACT_CODES[act], SE_GATE_CODES[gate_fn], B, C,
+                                       S, _ptr(out), current_stream_ptr(mean.device),
+                                       0 if w2t is None else 1, int(config)), 'mtr_se_gate_opts')
     return out
 
 
@@ -695,11 +702,26 @@ def conv1x1_supported(x, weight):
             and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
 
 
-def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None):
+CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3}
+
+
+def conv1x1_plan(M, K, HW, B, config='auto'):
+    """(configuration name, waves along the channels, channels per workgroup, columns per workgroup) K13 runs a
+    shape with: the library's own choice, or what a forced `config` resolves to.  Host only."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    check(_lib.load().mtr_conv1x1_plan(M, K, HW, B, CONV1X1_CONFIGS[config], ctypes.addressof(plan)),
+          'mtr_conv1x1_plan')
+    names = {v: k for k, v in CONV1X1_CONFIGS.items()}
+    return names[plan[0]], plan[1], plan[2], plan[3]
+
+
+def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config='auto'):
     """y = act(conv1x1(x * gate[:, :, None, None], w) + bias) (+ residual) in one launch on the current
     stream: x [B, K, H, W] f32 NCHW-contiguous, w [M, K] (or the [M, K, 1, 1] conv weight), bias [M],
     gate [B, K] f32 or None, residual [B, M, H, W] or None.  Stride 1, no padding; an f32 MFMA GEMM
-    in a fixed k order (the same bits on every call and graph replay)."""
+    in a fixed k order (the same bits on every call and graph replay, and for every `config`: a key of
+    CONV1X1_CONFIGS, 'auto' the library's own choice)."""
     require_cuda(x, w, bias, gate, residual)
     B, K, H, W = x.shape
     M = w.shape[0]
@@ -715,10 +737,11 @@ def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None):
         out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
     elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
         raise ValueError('conv1x1_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
-    check(_lib.load().mtr_conv1x1_bias_act(
+    check(_lib.load().mtr_conv1x1_bias_act_opts(
         _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
         None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
-        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act')
+        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device), CONV1X1_CONFIGS[config]),
+        'mtr_conv1x1_bias_act_opts')
     return out
 
 

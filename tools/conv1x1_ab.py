@@ -57,6 +57,8 @@ def main():
     ap.add_argument('--backbone', default='effnetv2-s')
     ap.add_argument('--timing', choices=['graph', 'eager'], default=None,
                     help='default: graph for f16 / bf16, eager for f32')
+    ap.add_argument('--config', default='auto', help='f32: K13 configurations to time, comma-separated')
+    ap.add_argument('--max-hw', type=int, default=None)
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -70,8 +72,11 @@ def main():
     timing = args.timing or ('eager' if dt == torch.float32 else 'graph')
     pinned = dt == torch.float32
     rows = []
+    configs = args.config.split(',') if dt == torch.float32 else ['auto']
     g = torch.Generator(device='cuda').manual_seed(0)
     for (K, M, H, W, act, res, gated), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+        if args.max_hw is not None and H * W > args.max_hw:
+            continue
         B = args.batch
         x = torch.randn(B, K, H, W, device='cuda', generator=g).to(dt)
         w = (torch.randn(M, K, 1, 1, device='cuda', generator=g) / K ** 0.5).to(dt)
@@ -86,10 +91,12 @@ def main():
             kernels.bias_act_(yy, b, act, r)
             return yy
 
-        def new():
+        def new(config=configs[0]):
             if dt != torch.float32:
                 return kernels.conv1x1_bias_act16(x, w, b, act, gate=gate, residual=r, out=y)
-            return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y)
+            return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y, config=config)
+
+        extra = {c: (lambda c=c: new(c)) for c in configs[1:]}
 
         def captured(fn):
             """--iters calls of fn as one HIP graph (fn has run eagerly before: lazy set-up is done)."""
@@ -122,16 +129,23 @@ def main():
             a, c = old(), new()
             torch.cuda.synchronize()
             diff = float((a - c).abs().max().float() / a.abs().max().float().clamp_min(1e-30))
+            for fn in extra.values():
+                assert torch.equal(fn().clone(), c)   # every configuration returns the same bits
             for _ in range(3):
                 old(), new()
             arm_old, arm_new = (captured(old), captured(new)) if timing == 'graph' else (old, new)
+            arm_extra = {c: captured(fn) if timing == 'graph' else fn for c, fn in extra.items()}
             for _ in range(2):
                 timed(arm_old), timed(arm_new)
-            t_old, t_new = [], []
+                for fn in arm_extra.values():
+                    timed(fn)
+            t_old, t_new, t_extra = [], [], {c: [] for c in extra}
             for _ in range(args.rounds):
                 t_old.append(timed(arm_old))
                 t_new.append(timed(arm_new))
-            del arm_old, arm_new
+                for c, fn in arm_extra.items():
+                    t_extra[c].append(timed(fn))
+            del arm_old, arm_new, arm_extra
         med = lambda v: sorted(v)[len(v) // 2]
         flop = 2.0 * B * H * W * K * M
         byts = x.element_size() * (B * H * W * (K + M * (2 if res else 1)) + M * K)
@@ -142,6 +156,13 @@ def main():
                                                    f'{k}_tflops': round(flop / med(t_new) / 1e6, 1),
                                                    f'{k}_share_of_peak': round(flop / med(t_new) / 1e6 / peak, 3)},
                    floor_us=round(floor, 2), speedup=round(med(t_old) / med(t_new), 3), rel_diff=diff)
+        if dt == torch.float32:
+            row.update(config=configs[0], plan=list(kernels.conv1x1_plan(M, K, H * W, B, configs[0])), timing=timing,
+                       wins_every_round=all(n < o for n, o in zip(t_new, t_old)))
+            for c, v in t_extra.items():
+                row[f'k13_{c}_us'] = round(med(v), 2)
+                row[f'k13_{c}_plan'] = list(kernels.conv1x1_plan(M, K, H * W, B, c))
+                row[f'k13_{c}_wins_every_round'] = all(n < o for n, o in zip(v, t_old))
         if dt != torch.float32:
             row.update(dtype=args.dtype, batch=B, res=args.res, timing=timing, library_pinned=pinned, hbm_tbs=HBM_TBS,
                        byte_floor_us=round(byte_floor, 2), share_of_byte_floor=round(byte_floor / med(t_new), 3))
