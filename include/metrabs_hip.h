@@ -598,6 +598,30 @@ int mtr_conv3x3_bias_act16(const void* x, int dtype, const void* weight /*[Cout]
  * entry has no kernel for it and answers MTR_E_SHAPE.  No GPU work. */
 size_t mtr_conv3x3_16_lds_bytes(long long B, int Cin, int Cout, int H, int W, int stride);
 
+/* K16h (outside the reference's hot path, like K10): a whole FusedMBConv block of f16 / bf16 tensors -- the dense
+ * 3x3 expand of K14h and the 1x1 project of K13h behind it -- as ONE launch; the Cmid-wide activation between them
+ * stays in LDS (no workspace, nothing allocated, graph-capturable):
+ *   mid[b, c, p] = rnd16(act(bias3[c] + conv3x3(x, w3, stride, pad 1)[b, c, p]))              c < Cmid
+ *   y[b, m, p]   = rnd16(bias1[m] + sum_c w1[m, c] * mid[b, c, p] (+ residual[b, m, p]))       m < Cout
+ * The result has the BITS of mtr_conv3x3_bias_act16(x, w3_packed, bias3, NULL, act) followed by
+ * mtr_conv1x1_bias_act16(mid, w1, bias1, NULL, residual, MTR_ACT none): the same 16-k MFMA steps in the same order,
+ * the intermediate rounded to 16 bits once, the same epilogue order; it does not depend on the tile picked.
+ * x [B, Cin, H, W], y and residual [B, Cout, Ho, Wo] (NCHW, contiguous, 16-byte aligned) in `dtype` (MTR_F16 or
+ * MTR_BF16, else MTR_E_DTYPE); w3_packed [Cmid][3][3][Cin] as K14h takes it, w1 [Cout][Cmid], both in `dtype` and
+ * 16-byte aligned; bias3 [Cmid] and bias1 [Cout] f32.  `act` is the expand's activation; the project has none.
+ * MTR_E_SHAPE (the caller keeps the two-kernel chain) unless: stride 1 or 2; Cin and Cmid multiples of 8; W and Wo
+ * multiples of 4; Cout <= 128; the input halo of a 128-position tile plus one chunk of `mid` (128 positions x 128 or
+ * 192 channels) within 160 KiB of LDS (mtr_fused_mbconv16_lds_bytes tells); a residual only with stride 1 and
+ * Cout == Cin.  residual may be NULL and may be x itself; y must not alias x or residual.  No atomics, no split-K. */
+int mtr_fused_mbconv16(const void* x, int dtype, const void* w3_packed /*[Cmid][3][3][Cin]*/, const float* bias3,
+                       int act, const void* w1 /*[Cout][Cmid]*/, const float* bias1, const void* residual,
+                       long long B, int Cin, int Cmid, int Cout, int H, int W, int stride, void* y,
+                       mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_fused_mbconv16 uses for this shape (the staged halo and one chunk of the
+ * intermediate), or 0 where the entry has no kernel for it and answers MTR_E_SHAPE.  No GPU work. */
+size_t mtr_fused_mbconv16_lds_bytes(long long B, int Cin, int Cmid, int Cout, int H, int W, int stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,9 @@ SIGNATURES = {
     'mtr_conv3x3_bias_act16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                        c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_conv3x3_16_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int]),
+    'mtr_fused_mbconv16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_fused_mbconv16_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

@@ -158,7 +158,44 @@ class FusedMBConv(nn.Module):
             layers['1'] = ConvBNAct(mid, cout, 1, 1, act=None)
         self.block = nn.Sequential(layers)
 
+    # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
+    # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
+    fused_pair = ()
+    # 'k16h' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on every other block
+    last_path = None
+    # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
+    use_k16h = True
+    # (Cin, Cmid, Cout, stride, H, W) of the input where K16h measured slower than the chain as the default copy
+    # runs it in f16 or bf16, both timed as HIP graph replays
+    k16h_slower = frozenset()
+
+    def k16h_takes(self, x):
+        """Whether forward(x) runs the armed block as one launch (K16h, fused_mbconv16.hip): a CUDA NCHW-contiguous
+        input of the copy's dtype, autocast off, no gradient wanted, a shape the C entry accepts and that is not
+        listed as slower."""
+        if not (self.fused_pair and FusedMBConv.use_k16h and x.is_cuda and x.dim() == 4):
+            return False
+        expand, project = self.fused_pair
+        w3, w1 = expand.conv.weight, project.conv.weight
+        if x.dtype != w3.dtype or w1.dtype != w3.dtype or x.dtype not in (torch.float16, torch.bfloat16):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (w3.requires_grad or w1.requires_grad)):
+            return False
+        if (w3.shape[1], w3.shape[0], w1.shape[0], expand.stride, x.shape[2], x.shape[3]) in FusedMBConv.k16h_slower:
+            return False
+        from . import kernels
+        return kernels.fused_mbconv16_supported(x, expand.weight_packed, w1, expand.stride)
+
     def forward(self, x):
+        if self.fused_pair:
+            if self.k16h_takes(x):
+                from . import kernels
+                expand, project = self.fused_pair
+                self.last_path = 'k16h'
+                return kernels.fused_mbconv16(x, expand.weight_packed, expand.bias, expand.act_name, expand.stride,
+                                              project.conv.weight, project.bias,
+                                              residual=x if self.residual else None)
+            self.last_path = 'chain'
         return _block_plus_skip(self.block, x) if self.residual else self.block(x)
 
 
@@ -567,7 +604,7 @@ def _block_plus_skip(block, x):
     return x + block(x)
 
 
-def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
+def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -581,7 +618,11 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
     3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise 3x3 and 5x5 layers (K11,
     K15) and the squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast
     at the first convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense
-    3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h."""
+    3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h.
+    fuse_blocks=True (needs a 16-bit dtype; off by default) additionally arms every FusedMBConv whose block is
+    exactly a Conv3x3BiasAct expand and a ConvBiasAct project without activation: such a block runs as ONE launch
+    (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and the chain everywhere
+    else.  The module tree and the state_dict are those of the copy without the option."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -590,6 +631,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
         raise ValueError(f'fold_batchnorm: dtype must be None, torch.float16 or torch.bfloat16, got {dtype}')
     if dtype is not None and not fused_epilogue:
         raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
+    if fuse_blocks and dtype is None:
+        raise ValueError('fold_batchnorm: fuse_blocks=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -649,6 +692,18 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None):
                     and Conv3x3BiasAct.applies_to(m[0].conv):
                 m[0] = Conv3x3BiasAct(m[0].conv, m[0].bias, m[0].act)
         folded.inference_dtype = dtype
+    if fuse_blocks:  # expand 3x3 -> project 1x1 of a FusedMBConv: one launch (K16h)
+        for m in folded.modules():
+            if isinstance(m, FusedMBConv) and list(m.block._modules) == ['0', '1']:
+                first, last = m.block._modules['0'], m.block._modules['1']
+                if isinstance(first, ConvBNAct) and isinstance(last, ConvBNAct) \
+                        and isinstance(first[0], Conv3x3BiasAct) and isinstance(last[0], ConvBiasAct) \
+                        and all(isinstance(k, nn.Identity) for k in list(first)[1:] + list(last)[1:]) \
+                        and last[0].act is None and not last[0].emit_mean \
+                        and last[0].conv.kernel_size == (1, 1) and last[0].conv.stride == (1, 1) \
+                        and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
+                        and last[0].conv.in_channels == first[0].conv.out_channels:
+                    m.fused_pair = (first[0], last[0])
     return folded
 
 

@@ -846,3 +846,68 @@ def conv3x3_bias_act16(x, w_packed, bias, act, stride, residual=None, out=None):
         None if residual is None else _ptr(residual), ACT_CODES[act], B, K, M, H, W, int(stride), _ptr(out),
         current_stream_ptr(x.device)), 'mtr_conv3x3_bias_act16')
     return out
+
+
+# K16h: a FusedMBConv block of f16 / bf16 tensors -- K14h's 3x3 expand and K13h's 1x1 project -- as one launch
+# (csrc/fused_mbconv16.hip)
+
+def fused_mbconv16_supported(x, w3_packed, w1, stride):
+    """Whether mtr_fused_mbconv16 takes this input: f16 or bf16 x and weights of one dtype, x NCHW-contiguous and
+    16-byte aligned, stride 1 or 2, Cin and Cmid multiples of 8, the input and output widths multiples of 4,
+    Cout <= 128, the input halo of a tile and one chunk of the intermediate within LDS (its MTR_E_DTYPE /
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w3_packed` is the expand's weight packed
+    [Cmid, 3, 3, Cin] (pack_conv3x3_weight), `w1` the project's, [Cout, Cmid] or [Cout, Cmid, 1, 1]."""
+    if x.dim() != 4 or w3_packed.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) \
+            or w3_packed.dtype != x.dtype or w1.dtype != x.dtype or not x.is_contiguous() \
+            or not w3_packed.is_contiguous() or not w1.is_contiguous() \
+            or x.data_ptr() % 16 or w3_packed.data_ptr() % 16 or w1.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    Cmid, Cout = w3_packed.shape[0], w1.shape[0]
+    if tuple(w3_packed.shape[1:]) != (3, 3, K) or w1.numel() != Cout * Cmid or B >= 2 ** 16:
+        return False
+    return _lib.load().mtr_fused_mbconv16_lds_bytes(B, K, Cmid, Cout, H, W, int(stride)) > 0
+
+
+def fused_mbconv16(x, w3_packed, bias3, act, stride, w1, bias1, residual=None, out=None):
+    """y = conv1x1(act(conv3x3(x, w3, stride, padding 1) + bias3), w1) + bias1 (+ residual) in one launch on the
+    current stream, for f16 / bf16: x [B, Cin, H, W] NCHW-contiguous, w3_packed [Cmid, 3, 3, Cin]
+    (pack_conv3x3_weight) and w1 [Cout, Cmid] (or the [Cout, Cmid, 1, 1] conv weight) in x's dtype, bias3 [Cmid]
+    and bias1 [Cout] f32, residual [B, Cout, Ho, Wo] in x's dtype or None (stride 1 and Cout == Cin only; it may be
+    x itself).  The intermediate stays on the chip, rounded to x's dtype once; the result has the bits of
+    conv3x3_bias_act16 followed by conv1x1_bias_act16 (the same on every call and graph replay)."""
+    require_cuda(x, w3_packed, bias3, w1, bias1, residual)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('fused_mbconv16: x must be [B, Cin, H, W], NCHW-contiguous')
+    B, K, H, W = x.shape
+    Cmid = w3_packed.shape[0]
+    if w3_packed.dim() != 4 or tuple(w3_packed.shape[1:]) != (3, 3, K) or not w3_packed.is_contiguous():
+        raise ValueError(f'fused_mbconv16: the 3x3 weight must be packed [Cmid, 3, 3, {K}] and contiguous, '
+                         f'got {tuple(w3_packed.shape)}')
+    M = w1.shape[0]
+    w1 = w1.reshape(M, -1)
+    if w1.shape[1] != Cmid:
+        raise ValueError(f'fused_mbconv16: the 1x1 weight has {w1.shape[1]} input channels, the 3x3 weight '
+                         f'{Cmid} output channels')
+    if w3_packed.dtype != x.dtype or w1.dtype != x.dtype:
+        raise ValueError(f'fused_mbconv16: weights are {w3_packed.dtype} and {w1.dtype}, x is {x.dtype}')
+    if stride not in (1, 2):
+        raise ValueError(f'fused_mbconv16: stride must be 1 or 2, got {stride}')
+    if bias3.numel() != Cmid or bias1.numel() != M:
+        raise ValueError(f'fused_mbconv16: biases have {bias3.numel()} and {bias1.numel()} elements, expected '
+                         f'{Cmid} and {M}')
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if residual is not None:
+        if stride != 1 or M != K:
+            raise ValueError('fused_mbconv16: a residual needs stride 1 and Cout == Cin')
+        if residual.shape != (B, M, Ho, Wo) or residual.dtype != x.dtype or not residual.is_contiguous():
+            raise ValueError('fused_mbconv16: residual must be [B, Cout, Ho, Wo] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, Ho, Wo, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, Ho, Wo) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('fused_mbconv16: out must be [B, Cout, Ho, Wo] like the output, contiguous')
+    check(_lib.load().mtr_fused_mbconv16(
+        _ptr(x), dtype_code(x.dtype), _ptr(w3_packed), _ptr(bias3.contiguous().float()), ACT_CODES[act],
+        _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), None if residual is None else _ptr(residual),
+        B, K, Cmid, M, H, W, int(stride), _ptr(out), current_stream_ptr(x.device)), 'mtr_fused_mbconv16')
+    return out

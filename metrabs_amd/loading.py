@@ -54,19 +54,24 @@ def load_joint_info(model_dir):
     return JointInfo(ji['joint_names'], ji['joint_edges'])
 
 
-def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None):
+def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
+                    fuse_blocks=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
     rounding, ~12 % less backbone time; fused_epilogue=True also runs bias + activation behind the
     folded convolutions as one in-place HIP pass, K10); the default keeps the checkpoint's own
     arithmetic.  dtype=torch.float16 / torch.bfloat16 always gives the 16-bit folded copy with fused
-    epilogues (backbones.fold_batchnorm(dtype=)), whatever fold_batchnorm and fused_epilogue say."""
+    epilogues (backbones.fold_batchnorm(dtype=)), whatever fold_batchnorm and fused_epilogue say.
+    fuse_blocks=True (a 16-bit dtype only, else ValueError) also runs its FusedMBConv blocks as one launch each
+    (backbones.fold_batchnorm(fuse_blocks=True), K16h): the same bits, off by default."""
     if dtype == torch.float32:
         dtype = None
     if dtype not in (None, torch.float16, torch.bfloat16):
         raise ValueError(f'load_crop_model: dtype must be None, torch.float32, torch.float16 or torch.bfloat16, '
                          f'got {dtype}')
+    if fuse_blocks and dtype is None:
+        raise ValueError('load_crop_model: fuse_blocks=True needs dtype=torch.float16 or torch.bfloat16')
     cfg, raw = load_config(model_dir)
     # config.affine_weights (models/metrabs.py:23-32) is a path or a name under $DATA_ROOT/skeleton_conversion;
     # a file of that name shipped INSIDE the model directory is found too
@@ -84,7 +89,7 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     model = model.eval()
     if dtype is not None:
         from .backbones import fold_batchnorm as fold
-        model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype)
+        model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype, fuse_blocks=fuse_blocks)
     elif fold_batchnorm:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=fused_epilogue)
@@ -92,10 +97,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
 
 
 def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchnorm=False,
-                           fused_epilogue=False, dtype=None):
-    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype: as load_crop_model (a 16-bit copy also
-    makes the estimator sample 16-bit crops)."""
-    model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype)
+                           fused_epilogue=False, dtype=None, fuse_blocks=False):
+    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks: as load_crop_model (a 16-bit copy
+    also makes the estimator sample 16-bit crops)."""
+    model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
+                            fuse_blocks=fuse_blocks)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

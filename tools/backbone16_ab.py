@@ -15,6 +15,9 @@ the graph cache's replay counts are reported with each pair.  bench.py itself is
 are folded from the same network, A with DepthwiseBiasAct.kernel_sizes = (3,) at fold time (the 5x5 layers as
 DepthwiseConv2d + K10, the tree from before K15), B with (3, 5) (K15); --dtype f32 compares the f32 copies, f16 /
 bf16 the 16-bit copies.  The rows carry ab='k15'.
+--ab k16h: both arms are the 16-bit copy of the same network, A folded as by default, B with fuse_blocks=True (its
+FusedMBConv blocks of stages 2 - 3 as one launch each, K16h, where FusedMBConv.k16h_slower does not list them).  The
+rows carry ab='k16h'.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -34,9 +37,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h'], default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
-                         "--dtype f32) folded without vs with K15")
+                         "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     if (args.dtype == 'f32' or args.config == 3) and args.ab != 'k15':
@@ -56,6 +59,13 @@ def main():
     if dt is not None:
         est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt)
         est_b.crop_dtype = est_b.crop_model.input_dtype          # ... as its 16-bit copy
+    if args.ab == 'k16h':                                        # both arms the 16-bit copy, B with its blocks armed
+        from metrabs_amd.backbones import FusedMBConv
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   fuse_blocks=True)
+        assert any(isinstance(m, FusedMBConv) and m.fused_pair for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -121,6 +131,13 @@ def main():
                        copy_graph_replays=est_b.graphs.stats['replays'])
             print(json.dumps(row), flush=True)
             rows.append(row)
+    if args.ab == 'k16h':
+        from metrabs_amd.backbones import FusedMBConv
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules()
+                 if isinstance(m, FusedMBConv) and m.fused_pair]
+        row = dict(kind='paths', ab='k16h', k16h=paths.count('k16h'), chain=paths.count('chain'))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
         for r in rows:

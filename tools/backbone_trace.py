@@ -56,7 +56,7 @@ def record(args):
     calibrate_batchnorm(net, args.res, dev,
                         samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
-                         dtype=dt if args.precision.endswith('-copy') else None)
+                         dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
         x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
@@ -122,6 +122,8 @@ def _kind(kname):
         return 'marker'
     if 'se_gate' in k:
         return 'se_gate'
+    if 'fused_mbconv16_kernel' in k:  # K16h: a whole FusedMBConv block (3x3 expand + 1x1 project) of the 16-bit copy
+        return 'K16h'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
         return 'K14h'
     if 'conv1x1_16_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
@@ -172,11 +174,17 @@ def _role(module, kind):
 
 def _fused_table(per_kernel, pat):
     """The FusedMBConv stages (1 - 3) and the stem: per block the dense 3x3 convolution (MIOpen's kernels, layout
-    transposes and casts included, or K14h), the K10 pass behind it and the 1x1 project with its epilogue."""
+    transposes and casts included, or K14h), the K10 pass behind it and the 1x1 project with its epilogue; K16h (the
+    whole block as one launch, `record --fuse-blocks`) is launched by the block itself and has its own column."""
+    block_pat = re.compile(r'^1\.(\d+)\.(\d+)$')
     rows = OrderedDict()
     served = defaultdict(float)   # what serves the dense convolutions: kernel name (shortened) -> us
     for module, kind, kname, us in per_kernel:
         m = pat.match(module)
+        mb = block_pat.match(module) if kind == 'K16h' else None
+        if mb:
+            rows.setdefault(f'{mb.group(1)}.{mb.group(2)}', defaultdict(float))['K16h'] += us
+            continue
         if m and int(m.group(1)) < 4:
             key, layer = f'{m.group(1)}.{m.group(2)}', int(m.group(3))
         elif module.startswith('1.0.') or module == '1.0':
@@ -191,8 +199,9 @@ def _fused_table(per_kernel, pat):
         else:
             col = 'project'   # (K13h, or the library GEMM + K10)
         b[col] += us
-    cols = ['dense conv', 'K14h', 'K10', 'project']
-    lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project', '',
+    cols = ['dense conv', 'K14h', 'K10', 'project', 'K16h']
+    lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project '
+                 '(or K16h: all of them in one launch)', '',
              '| stage.block | ' + ' | '.join(cols) + ' | **3x3 + K10** |', '|---|' + '---|' * (len(cols) + 1)]
     sums = defaultdict(float)
     for key, b in rows.items():
@@ -206,6 +215,9 @@ def _fused_table(per_kernel, pat):
     lines.append('| **sum** | ' + ' | '.join(f'{sums[c]:.1f}' for c in cols) + f' | **{sums["dense"]:.1f}** |')
     lines += ['', f'Dense 3x3 layers of stages 1 - 3 with their epilogue (without the stem): '
                   f'**{sums["dense_blocks"]:.1f} us**.']
+    slice23 = sum(b['dense conv'] + b['K14h'] + b['K10'] + b['project'] + b['K16h']
+                  for key, b in rows.items() if key.split('.')[0] in ('2', '3'))
+    lines += ['', f'Dense 3x3 + project of stages 2 - 3 (K16h included): **{slice23:.1f} us**.']
     if served:
         lines += ['', 'Library kernels behind the "dense conv" column of stages 1 - 3 (kind: kernel, us):', '']
         lines += [f'- `{k}` {v:.1f}' for k, v in sorted(served.items(), key=lambda kv: -kv[1])[:8]]
@@ -331,6 +343,8 @@ def main():
     r.add_argument('--res', type=int, default=256)
     r.add_argument('--warmup', type=int, default=3)
     r.add_argument('--backbone', default='effnetv2-s')
+    r.add_argument('--fuse-blocks', action='store_true',
+                   help='fold with fuse_blocks=True (a -copy precision only): the armed FusedMBConv blocks on K16h')
     r.add_argument('--no-k15', action='store_true',
                    help='fold with DepthwiseBiasAct.kernel_sizes = (3,): 5x5 depthwise layers on DepthwiseConv2d + K10')
     r.add_argument('--precision', default='f32',
