@@ -622,6 +622,32 @@ int mtr_fused_mbconv16(const void* x, int dtype, const void* w3_packed /*[Cmid][
  * intermediate), or 0 where the entry has no kernel for it and answers MTR_E_SHAPE.  No GPU work. */
 size_t mtr_fused_mbconv16_lds_bytes(long long B, int Cin, int Cmid, int Cout, int H, int W, int stride);
 
+/* K17 (outside the reference's hot path, like K10): the backbone stem -- Preproc (x * 2 - 1) and the dense 3x3,
+ * stride-2, padding-1, Cin = 3 convolution behind it, with the K10 epilogue folded in -- as ONE launch:
+ *   p[b, ci, iy, ix] = preproc ? rndD(rndX(fma(2, x[b, ci, iy, ix], -1))) : rndD(x[b, ci, iy, ix])   inside the image
+ *                    = 0                                                  outside (the ring is zero AFTER Preproc)
+ *   y[b, m, oy, ox]  = rndD(act(bias[m] + sum_{ci, ky, kx} weight[m, ci, ky, kx] * p[b, ci, 2 oy + ky - 1, 2 ox + kx - 1]))
+ * rndX rounds to x_dtype, rndD to `dtype`: p has the bits of torch's (x * 2 - 1).to(dtype).  x is [B, 3, H, W]
+ * (layout MTR_NCHW) or interleaved [B, H, W, 3] (MTR_NHWC), contiguous, 16-byte aligned, in x_dtype; y is
+ * [B, Cout, H / 2, W / 2], NCHW-contiguous, 16-byte aligned, in `dtype`; weight is the convolution weight as stored,
+ * OIHW [Cout, 3, 3, 3], in `dtype`; bias [Cout] f32.  dtype MTR_F32, MTR_F16 or MTR_BF16; x_dtype == dtype, or
+ * MTR_F32 with a 16-bit dtype (the cast of the first convolution is folded in); else MTR_E_DTYPE.  The sum is
+ * accumulated in f32 in the one order k = 9 ci + 3 ky + kx (16-bit: two 16-k MFMA steps, K padded to 32 with zeros;
+ * f32: fourteen 2-k steps of the f32 MFMA, K padded to 28), the epilogue is f32 in K10's order, rounded to `dtype` once.  act: as mtr_bias_act_nchw;
+ * preproc 0 or 1.  MTR_E_SHAPE (the caller keeps the library chain) unless Cin == 3, H even, W % 8 == 0,
+ * Cout % 8 == 0, Cout <= 64, B <= 65535 and a band of input rows fits LDS (mtr_stem_conv_lds_bytes tells).  y must
+ * not overlap x (MTR_E_PARAM).  Every check is made on the host before anything is enqueued.  No atomics, no
+ * workspace, nothing allocated; only enqueues on `stream`: the same inputs give the same bits, for either layout,
+ * any batch index and on every graph replay. */
+int mtr_stem_conv3x3s2(const void* x, int x_dtype, int layout, const void* weight /*[Cout][3][3][3]*/,
+                       const float* bias, int dtype, int act, int preproc, long long B, int Cin, int Cout, int H,
+                       int W, void* y, mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_stem_conv3x3s2 uses for this shape and `dtype` (the staged band of input rows
+ * and the output turn), or 0 where the entry has no kernel for it and answers MTR_E_SHAPE / MTR_E_DTYPE.  No GPU
+ * work. */
+size_t mtr_stem_conv_lds_bytes(int dtype, long long B, int Cin, int Cout, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,9 @@ SIGNATURES = {
     'mtr_fused_mbconv16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                    ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_fused_mbconv16_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'mtr_stem_conv3x3s2': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_stem_conv_lds_bytes': (ctypes.c_size_t, [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

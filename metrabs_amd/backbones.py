@@ -223,7 +223,16 @@ class MBConv(nn.Module):
 class Preproc(nn.Module):
     """PreprocLayer (efficientnet.py:1181-1186): [0,1] -> [-1,1]."""
 
+    # set by fold_batchnorm(fuse_stem=True): the StemConvBiasAct directly behind this layer, which applies
+    # x * 2 - 1 itself as it stages x (K17) -- a reference, as SqueezeExcite.mean_from: nothing is registered twice
+    hand_to = ()
+
     def forward(self, x):
+        for dst in self.hand_to:
+            if dst.k17_takes(x):
+                # decided here, once: the stem convolution reads x in place and applies Preproc on the way in
+                dst.hand_over(x)
+                return x
         return x * 2 - 1
 
 
@@ -521,6 +530,62 @@ class Conv3x3BiasAct(nn.Module):
         return _library_conv_bias_act(self, x, residual)
 
 
+class StemConvBiasAct(ConvBiasAct):
+    """The folded stem -- a dense 3x3, stride-2, padding-1, Cin = 3 conv + BN + activation -- of a copy made with
+    fold_batchnorm(fuse_stem=True): Preproc, the convolution, "+ bias" and the activation as ONE HIP launch (K17,
+    stem_conv.hip) instead of an elementwise pass, a MIOpen convolution and K10.  K17 reads contiguous and
+    channels_last (interleaved) crops in place and writes an NCHW-contiguous activation.  Same parameters and
+    state_dict keys as the ConvBiasAct it replaces, which it also is for every input K17 does not take -- CPU,
+    autocast, a gradient wanted, odd shapes, other strides: those run exactly what ConvBiasAct runs."""
+
+    # class-wide switch (tests and A/B runs): the library path everywhere
+    use_k17 = True
+    # (Cout, H, W) of the input where K17 measured slower than Preproc + MIOpen + K10 (DESIGN.md section 17).  Empty
+    # because no shape has been timed yet, not because every shape is ahead
+    k17_slower = frozenset()
+
+    def __init__(self, conv, bias, act):
+        super().__init__(conv, bias, act)
+        self._handed = None
+        self.last_path = None  # 'k17' or 'library': what the last forward ran (tests, A/B runs)
+
+    @staticmethod
+    def applies_to(conv):
+        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
+                and conv.dilation == (1, 1) and conv.stride == (2, 2) and conv.padding == (1, 1)
+                and conv.padding_mode == 'zeros' and conv.in_channels == 3)
+
+    def k17_takes(self, x):
+        """Whether forward(x) runs on K17: a CUDA input, contiguous or channels_last, of the copy's dtype (or f32 in
+        front of a 16-bit copy), autocast off, no gradient wanted, a shape the C entry accepts and that is not listed
+        as slower."""
+        c = self.conv
+        if not (StemConvBiasAct.use_k17 and x.is_cuda and x.dim() == 4 and c.bias is None and not self.emit_mean):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (c.weight.requires_grad
+                                                                               or x.requires_grad)):
+            return False
+        if (c.out_channels, x.shape[2], x.shape[3]) in StemConvBiasAct.k17_slower:
+            return False
+        from . import kernels
+        return kernels.stem_conv_supported(x, c.weight)
+
+    def hand_over(self, x):
+        """From the Preproc in front: `x` comes WITHOUT x * 2 - 1 applied; the next forward(x) applies it."""
+        self._handed = x
+
+    def forward(self, x, residual=None):
+        held, self._handed = self._handed, None
+        raw = held is not None and held is x  # Preproc left x * 2 - 1 to this module
+        if residual is None and self.k17_takes(x):
+            from . import kernels
+            self.last_path = 'k17'
+            return kernels.stem_conv_bias_act(x, self.conv.weight, self.bias, self.act_name, preproc=raw)
+        if raw:  # (Preproc asked k17_takes(x) before it handed x over; whatever changed since: never un-preprocessed)
+            x = x * 2 - 1
+        return super().forward(x, residual)
+
+
 class DepthwiseBiasAct(nn.Module):
     """A folded depthwise 3x3 (K11) or 5x5 (K15) conv + BN + activation as ONE HIP pass over the plane: the
     convolution, "+ bias", the activation and -- in front of a squeeze-excite block -- the
@@ -604,7 +669,7 @@ def _block_plus_skip(block, x):
     return x + block(x)
 
 
-def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False):
+def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -622,7 +687,12 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     fuse_blocks=True (needs a 16-bit dtype; off by default) additionally arms every FusedMBConv whose block is
     exactly a Conv3x3BiasAct expand and a ConvBiasAct project without activation: such a block runs as ONE launch
     (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and the chain everywhere
-    else.  The module tree and the state_dict are those of the copy without the option."""
+    else.  The module tree and the state_dict are those of the copy without the option.
+    fuse_stem=True (needs fused_epilogue=True; any dtype; off by default; independent of fuse_blocks) makes the stem
+    -- the first dense 3x3 stride-2 padding-1 Cin = 3 ConvBiasAct -- a StemConvBiasAct, which runs Preproc, the
+    convolution and its epilogue as ONE launch (K17) where that kernel takes the input and the library chain
+    everywhere else, and arms the Preproc directly in front of it to hand its input over untouched.  The
+    state_dict keys are those of the copy without the option."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -633,6 +703,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
     if fuse_blocks and dtype is None:
         raise ValueError('fold_batchnorm: fuse_blocks=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
+    if fuse_stem and not fused_epilogue:
+        raise ValueError('fold_batchnorm: fuse_stem=True needs fused_epilogue=True')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -704,6 +776,20 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                         and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
                         and last[0].conv.in_channels == first[0].conv.out_channels:
                     m.fused_pair = (first[0], last[0])
+    if fuse_stem:  # Preproc -> stem 3x3 stride 2: one launch (K17)
+        stem_blk = next((m for m in folded.modules() if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct
+                         and not m[0].emit_mean and StemConvBiasAct.applies_to(m[0].conv)), None)
+        if stem_blk is not None:
+            stem_blk[0] = StemConvBiasAct(stem_blk[0].conv, stem_blk[0].bias, stem_blk[0].act)
+            for seq in folded.modules():
+                if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
+                    continue
+                kids = list(seq)
+                for prev, nxt in zip(kids, kids[1:]):
+                    while isinstance(nxt, nn.Sequential) and not isinstance(nxt, ConvBNAct) and len(nxt):
+                        nxt = nxt[0]  # (EfficientNetV2: Preproc stands in front of the `features` container)
+                    if isinstance(prev, Preproc) and nxt is stem_blk:
+                        prev.hand_to = (stem_blk[0],)
     return folded
 
 

@@ -911,3 +911,69 @@ def fused_mbconv16(x, w3_packed, bias3, act, stride, w1, bias1, residual=None, o
         _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), None if residual is None else _ptr(residual),
         B, K, Cmid, M, H, W, int(stride), _ptr(out), current_stream_ptr(x.device)), 'mtr_fused_mbconv16')
     return out
+
+
+# K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one
+# launch (csrc/stem_conv.hip)
+
+def _stem_layout(x):
+    """MTR_NCHW for a contiguous [B, 3, H, W], MTR_NHWC for a channels_last view over interleaved [B, H, W, 3]
+    memory, None for any other strides."""
+    if x.dim() != 4:
+        return None
+    if x.is_contiguous():
+        return _lib.MTR_NCHW
+    B, C, H, W = x.shape
+    sb, sc, sh, sw = x.stride()
+    if C == 3 and (sc, sh, sw) == (1, 3 * W, 3) and (B == 1 or sb == 3 * H * W):
+        return _lib.MTR_NHWC
+    return None
+
+
+def stem_conv_supported(x, weight):
+    """Whether mtr_stem_conv3x3s2 takes this input: CUDA tensors, x [B, 3, H, W] f32 / f16 / bf16, contiguous or channels_last
+    (interleaved [B, H, W, 3] memory), 16-byte aligned; weight OIHW [Cout, 3, 3, 3] contiguous, f32 / f16 / bf16,
+    of x's dtype or 16-bit with an f32 x; H even, W % 8 == 0, Cout % 8 == 0, Cout <= 64 (its MTR_E_DTYPE /
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
+    if not (x.is_cuda and weight.is_cuda):
+        return False
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 3, 3) or not weight.is_contiguous():
+        return False
+    ok = (torch.float32, torch.float16, torch.bfloat16)
+    if weight.dtype not in ok or x.dtype not in ok or not (x.dtype == weight.dtype or x.dtype == torch.float32):
+        return False
+    if _stem_layout(x) is None or x.data_ptr() % 16 or weight.data_ptr() % weight.element_size():
+        return False
+    B, K, H, W = x.shape
+    if B >= 2 ** 16:
+        return False
+    return _lib.load().mtr_stem_conv_lds_bytes(dtype_code(weight.dtype), B, K, weight.shape[0], H, W) > 0
+
+
+def stem_conv_bias_act(x, weight, bias, act, preproc=False, out=None):
+    """y = act(conv3x3(p, weight, stride 2, padding 1) + bias) in one launch on the current stream, where p is x, or
+    with preproc=True torch's (x * 2 - 1).to(weight.dtype) (the padding ring is zero after it): x [B, 3, H, W],
+    contiguous or channels_last, in the weight's dtype or f32; weight the OIHW [Cout, 3, 3, 3] convolution weight
+    (f32, f16 or bf16); bias [Cout] f32.  The result is [B, Cout, H / 2, W / 2], NCHW-contiguous, in the weight's
+    dtype: f32 accumulation in a fixed k order, rounded once (the same bits for either layout, on every call and
+    graph replay)."""
+    require_cuda(x, weight, bias, out)
+    layout = _stem_layout(x)
+    if layout is None:
+        raise ValueError('stem_conv_bias_act: x must be [B, 3, H, W], contiguous or channels_last')
+    B, K, H, W = x.shape
+    M = weight.shape[0]
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (K, 3, 3) or not weight.is_contiguous():
+        raise ValueError(f'stem_conv_bias_act: the weight must be [Cout, {K}, 3, 3] and contiguous, '
+                         f'got {tuple(weight.shape)}')
+    if bias.numel() != M:
+        raise ValueError(f'stem_conv_bias_act: bias has {bias.numel()} elements, expected {M}')
+    if out is None:
+        out = torch.empty(B, M, H // 2, W // 2, device=x.device, dtype=weight.dtype)
+    elif out.shape != (B, M, H // 2, W // 2) or out.dtype != weight.dtype or not out.is_contiguous():
+        raise ValueError('stem_conv_bias_act: out must be [B, Cout, H / 2, W / 2] in the weight\'s dtype, contiguous')
+    check(_lib.load().mtr_stem_conv3x3s2(
+        _ptr(x), dtype_code(x.dtype), layout, _ptr(weight), _ptr(bias.contiguous().float()),
+        dtype_code(weight.dtype), ACT_CODES[act], int(bool(preproc)), B, K, M, H, W, _ptr(out),
+        current_stream_ptr(x.device)), 'mtr_stem_conv3x3s2')
+    return out

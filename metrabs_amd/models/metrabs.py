@@ -351,7 +351,12 @@ class Metrabs(torch.nn.Module):
         this one.  The interleaved crops are handed to the backbone as the NCHW VIEW of the same memory
         (torch channels_last: no layout copy), the crop model runs under 16-bit autocast (the exported TF
         model's mixed_float16 policy; `autocast_dtype` if the model names one) and the head consumes the
-        NHWC 16-bit features in place."""
+        NHWC 16-bit features in place.  A 16-bit copy (loading.load_crop_model(dtype=)) runs in its own dtype
+        without autocast; its library stem returns a channels_last activation, which none of the copy's
+        NCHW kernels (K13h, K14h) takes, so the whole backbone stays on the library path.  On a copy made with
+        fuse_stem=True the interleaved crops are read in place by K17 (backbones.StemConvBiasAct), which writes an
+        NCHW-contiguous activation: the rest of the network then runs the copy's own kernels and the head
+        receives NCHW features."""
         if image.dtype != torch.float16 or image.dim() != 4 or image.shape[-1] != 3:
             raise TypeError(f'predict_multi: image must be float16 [N, H, W, 3], got {image.dtype} '
                             f'{tuple(image.shape)}')

@@ -18,6 +18,9 @@ bf16 the 16-bit copies.  The rows carry ab='k15'.
 --ab k16h: both arms are the 16-bit copy of the same network, A folded as by default, B with fuse_blocks=True (its
 FusedMBConv blocks of stages 2 - 3 as one launch each, K16h, where FusedMBConv.k16h_slower does not list them).  The
 rows carry ab='k16h'.
+--ab k17: both arms are the same copy of the same network (16-bit, or f32 with --dtype f32; --config 1, 3 or 4), A
+folded as by default, B with fuse_stem=True (Preproc + the stem convolution + its epilogue as one launch, K17).  The
+rows carry ab='k17'.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -37,13 +40,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17'], default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
-                         "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks")
+                         "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    if (args.dtype == 'f32' or args.config == 3) and args.ab != 'k15':
-        ap.error('--dtype f32 and --config 3 go with --ab k15')
+    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17'):
+        ap.error('--dtype f32 and --config 3 go with --ab k15 or --ab k17')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -66,6 +69,16 @@ def main():
         est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
                                                    fuse_blocks=True)
         assert any(isinstance(m, FusedMBConv) and m.fused_pair for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k17':                                         # both arms the same copy, B with its stem on K17
+        from metrabs_amd.backbones import StemConvBiasAct
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   fuse_stem=True)
+        for e in (est_a, est_b):
+            e.crop_dtype = e.crop_model.input_dtype
+            if dt is None:
+                e.crop_model.autocast_dtype = None               # f32 copies, run in f32
+        assert any(isinstance(m, StemConvBiasAct) for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -136,6 +149,12 @@ def main():
         paths = [m.last_path for m in est_b.crop_model.backbone.modules()
                  if isinstance(m, FusedMBConv) and m.fused_pair]
         row = dict(kind='paths', ab='k16h', k16h=paths.count('k16h'), chain=paths.count('chain'))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k17':
+        from metrabs_amd.backbones import StemConvBiasAct
+        row = dict(kind='paths', ab='k17', stem=[m.last_path for m in est_b.crop_model.backbone.modules()
+                                                  if isinstance(m, StemConvBiasAct)])
         print(json.dumps(row), flush=True)
         rows.append(row)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -56,7 +56,8 @@ def record(args):
     calibrate_batchnorm(net, args.res, dev,
                         samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
-                         dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks)
+                         dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
+                         fuse_stem=args.fuse_stem)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
         x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
@@ -122,6 +123,8 @@ def _kind(kname):
         return 'marker'
     if 'se_gate' in k:
         return 'se_gate'
+    if 'stem_conv_kernel' in k:  # K17 (before the generic 'conv' match): Preproc + the stem 3x3 stride-2 conv + epilogue
+        return 'K17'
     if 'fused_mbconv16_kernel' in k:  # K16h: a whole FusedMBConv block (3x3 expand + 1x1 project) of the 16-bit copy
         return 'K16h'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
@@ -345,6 +348,8 @@ def main():
     r.add_argument('--backbone', default='effnetv2-s')
     r.add_argument('--fuse-blocks', action='store_true',
                    help='fold with fuse_blocks=True (a -copy precision only): the armed FusedMBConv blocks on K16h')
+    r.add_argument('--fuse-stem', action='store_true',
+                   help='fold with fuse_stem=True: Preproc + the stem convolution + its epilogue on K17')
     r.add_argument('--no-k15', action='store_true',
                    help='fold with DepthwiseBiasAct.kernel_sizes = (3,): 5x5 depthwise layers on DepthwiseConv2d + K10')
     r.add_argument('--precision', default='f32',
