@@ -156,6 +156,8 @@ SIGNATURES = {
                                  c_int, c_void_p, c_void_p, c_int, c_int]),
     'mtr_conv1x1_bias_act_opts': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    'mtr_conv1x1_bias_act_pre': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     'mtr_conv1x1_plan': (c_int, [c_int, c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
     'mtr_conv1x1_bias_act': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),

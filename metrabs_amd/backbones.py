@@ -161,7 +161,8 @@ class FusedMBConv(nn.Module):
     # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
     # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
     fused_pair = ()
-    # 'k16h' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on every other block
+    # 'k16h' / 'k13_pre' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on every
+    # other block
     last_path = None
     # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
     use_k16h = True
@@ -186,7 +187,40 @@ class FusedMBConv(nn.Module):
         from . import kernels
         return kernels.fused_mbconv16_supported(x, expand.weight_packed, w1, expand.stride)
 
+    # set by fold_batchnorm(fused_epilogue=True) on an f32 copy: (the block's 3x3 ConvBiasAct, its project
+    # ConvBiasAct) -- references, like fused_pair.  The 3x3 layer's K10 pass ("+ bias", activation) is left out and
+    # applied by the project's K13 launch to every element on its way into the GEMM: the same bits, one read and one
+    # write of the expanded activation less
+    pre_pair = ()
+    # class-wide switch (tests and A/B runs): K10 behind the 3x3 convolution everywhere
+    use_k13_pre = True
+    # (Cin, Cmid, Cout, stride, H, W) of the input where K13 with the prologue measured slower than K10 + K13 as HIP
+    # graph replays: these stay on the chain
+    k13_pre_slower = frozenset()
+
+    def _forward_pre(self, x):
+        """An armed f32 block.  'k13_pre': the 3x3 convolution alone, then ONE K13 launch that applies its epilogue,
+        the project and the skip.  'chain': what an unarmed block runs.  The tensor without its epilogue never leaves
+        this method."""
+        first, project = self.pre_pair
+        c = first.conv
+        residual = x if self.residual else None
+        self.last_path = 'chain'
+        if not (FusedMBConv.use_k13_pre and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+                and c.weight.dtype == torch.float32 and not torch.is_autocast_enabled('cuda')
+                and not (torch.is_grad_enabled() and (c.weight.requires_grad or x.requires_grad))
+                and (c.in_channels, c.out_channels, project.conv.out_channels, c.stride[0], x.shape[2], x.shape[3])
+                not in FusedMBConv.k13_pre_slower):
+            return _block_plus_skip(self.block, x) if self.residual else self.block(x)
+        y = first(x, defer_epilogue=True)
+        if project.k13_accepts(y, residual):
+            self.last_path = 'k13_pre'
+            return project(y, residual=residual, pre=first)
+        return project(_finish_bias_act(first, y, None), residual=residual)
+
     def forward(self, x):
+        if self.pre_pair:
+            return self._forward_pre(x)
         if self.fused_pair:
             if self.k16h_takes(x):
                 from . import kernels
@@ -383,6 +417,11 @@ class ConvBiasAct(nn.Module):
         from . import kernels
         return kernels.conv1x1_supported(x, c.weight)
 
+    def k13_accepts(self, x, residual):
+        """k13_takes(x), and a skip connection K13's epilogue can add: x's dtype, contiguous, 16-byte aligned."""
+        return self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                                           and residual.data_ptr() % 16 == 0))
+
     # class-wide switch (tests and A/B runs): 1x1 convolutions of a 16-bit copy on K13h instead of
     # rocBLAS + K10 (+ x * gate)
     use_k13h = True
@@ -426,7 +465,19 @@ class ConvBiasAct(nn.Module):
         m = self.take_mean_f32(x)
         return None if m is None else m.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
+        """defer_epilogue / pre: between the two layers of an armed FusedMBConv (FusedMBConv._forward_pre) only.
+        defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way,
+        and its "+ bias, activation" is applied here, inside K13: the block passes `pre` only after
+        k13_accepts(x, residual) said yes, and finishes x with K10 itself otherwise."""
+        if defer_epilogue:
+            self.last_path = 'library'
+            return self.conv(x)
+        if pre is not None:  # (the block asked k13_accepts(x, residual) for this very tensor)
+            from . import kernels
+            self._gate, self.last_path = None, 'k13'
+            return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, residual=residual,
+                                            in_bias=pre.bias, in_act=pre.act_name)
         held, self._gate = self._gate, None
         gate = held[1] if held is not None and held[0] is x else None
         w16 = self.conv.weight.dtype
@@ -438,8 +489,7 @@ class ConvBiasAct(nn.Module):
             self.last_path = 'k13h' if gate is None else 'k13h_gate'
             return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
                                               residual=residual)
-        if self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                                       and residual.data_ptr() % 16 == 0)):
+        if self.k13_accepts(x, residual):
             from . import kernels
             self.last_path = 'k13' if gate is None else 'k13_gate'
             return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, gate=gate,
@@ -453,7 +503,11 @@ class ConvBiasAct(nn.Module):
 def _library_conv_bias_act(mod, x, residual):
     """The library path of a folded convolution `mod` (ConvBiasAct, Conv3x3BiasAct): mod.conv (MIOpen / rocBLAS),
     then "+ bias, activation (, + residual)" as K10 where it applies, else the torch ops."""
-    y = mod.conv(x)
+    return _finish_bias_act(mod, mod.conv(x), residual)
+
+
+def _finish_bias_act(mod, y, residual):
+    """The epilogue of the library path on `y` = mod.conv(x)."""
     # K10 moves 16 bytes per lane: planes of a multiple of the vector width (7x7 maps at 224 px,
     # 5x5 at 160 px are not), 16-byte aligned storage; everything else takes the torch ops
     hw_vec_ok = (y.shape[2] * y.shape[3]) % (16 // y.element_size()) == 0
@@ -684,6 +738,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     K15) and the squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast
     at the first convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense
     3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h.
+    On an f32 copy (no dtype) fused_epilogue=True also arms every FusedMBConv whose block is exactly a dense 3x3
+    ConvBiasAct and a 1x1 ConvBiasAct project without activation: the 3x3 layer's K10 pass is left out and applied by
+    the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with the bits of
+    the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict.
     fuse_blocks=True (needs a 16-bit dtype; off by default) additionally arms every FusedMBConv whose block is
     exactly a Conv3x3BiasAct expand and a ConvBiasAct project without activation: such a block runs as ONE launch
     (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and the chain everywhere
@@ -755,6 +813,19 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                 if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and \
                         isinstance(nxt[0], ConvBiasAct):
                     prev.gate_to = (nxt[0],)
+    if fused_epilogue and dtype is None:  # dense 3x3 -> project 1x1 of a FusedMBConv: the 3x3's epilogue inside K13
+        for m in folded.modules():
+            if isinstance(m, FusedMBConv) and list(m.block._modules) == ['0', '1']:
+                first, last = m.block._modules['0'], m.block._modules['1']
+                if isinstance(first, ConvBNAct) and isinstance(last, ConvBNAct) \
+                        and type(first[0]) is ConvBiasAct and type(last[0]) is ConvBiasAct \
+                        and all(isinstance(k, nn.Identity) for k in list(first)[1:] + list(last)[1:]) \
+                        and first[0].conv.kernel_size == (3, 3) and first[0].conv.groups == 1 \
+                        and not first[0].emit_mean and last[0].act is None and not last[0].emit_mean \
+                        and last[0].conv.kernel_size == (1, 1) and last[0].conv.stride == (1, 1) \
+                        and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
+                        and last[0].conv.in_channels == first[0].conv.out_channels:
+                    m.pre_pair = (first[0], last[0])
     if dtype is not None:  # the 16-bit copy: GEMM / MIOpen weights cast once, not by autocast on every forward
         for m in folded.modules():
             if isinstance(m, ConvBiasAct):

@@ -22,6 +22,13 @@
 // past B * HW and k past K are zero-filled, never stored.  The configuration is a pure function of
 // (M, K, HW, B) (pick_config); the k order is 0, 1, 2, ... in every configuration, so the result does
 // not depend on it.  No atomics, no split-K: the same inputs give the same bits.
+//
+// The input prologue (template parameter PRE: -1 none, else an Act code): behind a dense 3x3 convolution
+// whose K10 pass ("+ bias", activation, in place) has been left out, every staged element of x becomes
+//   v = act_in(x[b, k, p] + in_bias[k])
+// made opaque with settled() -- the f32 value K10 would have stored -- and then v * gate[b, k] as above.
+// It is applied inside the bounds checks (or selected against zero, deep-K): a zero-filled entry stays zero.
+// PRE = -1 is the code from before the prologue existed.
 #include <type_traits>
 
 #include "common.h"
@@ -34,11 +41,11 @@ constexpr int kC1PadX = 32;  // X tile row pad (floats): the two lane halves rea
 constexpr int kC1PadW = 4;   // W^T tile row pad: the transposing writes of 4 k-rows land on distinct banks
 
 // WM x WN waves, each FM x FN tiles of 32 x 32 (channels x positions), k-tiles of BK
-template <int WM, int WN, int FM, int FN, int BK, int ACT>
+template <int WM, int WN, int FM, int FN, int BK, int ACT, int PRE>
 __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-    const float* __restrict__ gate, const float* __restrict__ residual, float* __restrict__ y, int M,
-    int K, int HW, int n_total, FastDiv by_hw) {
+    const float* __restrict__ in_bias, const float* __restrict__ gate, const float* __restrict__ residual,
+    float* __restrict__ y, int M, int K, int HW, int n_total, FastDiv by_hw) {
   constexpr int NT = 64 * WM * WN;
   constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
   constexpr int LDX = BN + kC1PadX, LDW = BM + kC1PadW;
@@ -74,6 +81,11 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
       float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       if (xcol_ok && k < K && xk0 + v * XPASS < BK) {
         t = *reinterpret_cast<const float4*>(xsrc + (long long)k * HW);
+        if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits
+          const float bi = in_bias[k];
+          t.x = settled(activate<PRE>(t.x + bi)); t.y = settled(activate<PRE>(t.y + bi));
+          t.z = settled(activate<PRE>(t.z + bi)); t.w = settled(activate<PRE>(t.w + bi));
+        }
         if (gsrc) {  // the squeeze-excite gate, once per staged element: x * g rounded as torch does
           const float g = gsrc[k];
           t.x *= g; t.y *= g; t.z *= g; t.w *= g;
@@ -189,11 +201,11 @@ constexpr size_t deepk_lds_bytes(int waves) {
   return (size_t)kDkStages * (kDkBK * kDkBN + 32 * waves * kDkLDW) * sizeof(float);
 }
 
-template <int WAVES, int ACT>
+template <int WAVES, int ACT, int PRE>
 __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-    const float* __restrict__ gate, const float* __restrict__ residual, float* __restrict__ y, int M,
-    int K, int HW, int n_total, FastDiv by_hw) {
+    const float* __restrict__ in_bias, const float* __restrict__ gate, const float* __restrict__ residual,
+    float* __restrict__ y, int M, int K, int HW, int n_total, FastDiv by_hw) {
   constexpr int NT = 64 * WAVES, BM = 32 * WAVES;
   constexpr int XS = kDkBK * kDkBN, WS = BM * kDkLDW;  // floats per stage
   static_assert(BM * (kDkBK / 4) == 4 * NT, "W loader mapping");
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
   // Two register sets (tiles t + 2 and t + 3 are in flight together), always indexed by a constant.
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 rw[2][4] = {{zero, zero, zero, zero}, {zero, zero, zero, zero}};
-  float rx[2][XV] = {}, rg[2] = {1.0f, 1.0f};
+  float rx[2][XV] = {}, rg[2] = {1.0f, 1.0f}, rbi[2] = {0.0f, 0.0f};
   auto load_tile = [&](int kt, auto set) {
     constexpr int P = decltype(set)::value;
     const int k0 = kt * kDkBK;
@@ -237,6 +249,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
       rx[P][0] = xsrc[(long long)kx * HW];
     }
     rg[P] = gsrc[kx];
+    if constexpr (PRE >= 0) rbi[P] = in_bias[kx];
     const int k = min(k0 + wk4 * 4, K - 4);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
@@ -250,10 +263,16 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
     const float g = has_gate ? rg[P] : 1.0f;  // the squeeze-excite gate, once per staged element: x * g rounded as torch does
     const bool x_ok = xcol_ok && k0 + xk < K;
     float* xd = &xs[stage * XS + xk * kDkBN + xp];
+    float v0 = rx[P][0], v1 = rx[P][XV - 1];
+    if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits.  A clamped
+      // load may give anything here (inf, NaN): it is selected away below, never multiplied to zero
+      v0 = settled(activate<PRE>(v0 + rbi[P]));
+      if constexpr (XV == 2) v1 = settled(activate<PRE>(v1 + rbi[P]));
+    }
     if constexpr (XV == 2) {
-      *reinterpret_cast<float2*>(xd) = make_float2(x_ok ? rx[P][0] * g : 0.0f, x_ok ? rx[P][XV - 1] * g : 0.0f);
+      *reinterpret_cast<float2*>(xd) = make_float2(x_ok ? v0 * g : 0.0f, x_ok ? v1 * g : 0.0f);
     } else {
-      *xd = x_ok ? rx[P][0] * g : 0.0f;
+      *xd = x_ok ? v0 * g : 0.0f;
     }
     const bool k_ok = k0 + wk4 * 4 < K;
 #pragma unroll
@@ -343,6 +362,154 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
   }
 }
 
+// The streaming configuration: short-K, few-channel projects (the FusedMBConv projects: K <= 256, M <= 64) whose whole
+// weight fits LDS.  There every element of x is used by one workgroup only, so its round trip through LDS in the
+// tiles above buys no reuse and costs a write, a barrier and a read per k-tile -- and with the input prologue the
+// staging threads' VALU work sits in front of that barrier.  Here a workgroup of four waves stages W^T ([k][m], zero
+// rows up to a multiple of 32 k, zero columns up to MT * 32) and in_bias into LDS ONCE, behind one barrier, and issues
+// no barrier after that.  Each wave owns 32 columns and ALL M rows (MT tiles of 32): lane l loads its A operand of
+// v_mfma_f32_32x32x2_f32 straight from global memory, x[k + (l >> 5)][p0 + (l & 31)] (two full 128-byte segments per
+// instruction), applies the prologue and the gate to that register and reads the B operand from LDS.  Loads run one
+// chunk of kStR k-steps (32 k, 4 KB per wave) ahead of the MFMAs in a second register set; they carry no condition: k
+// past K and columns past B * HW read a clamped address and are SELECTED to zero (act(0 + b) is not zero, 0 * inf is
+// NaN).  The k order is 0, 1, 2, ... and the accumulator layout that of conv1x1_kernel: the same bits, the same
+// epilogue.  A tile may span images (HW < 32): every lane derives its own image index.  `tiles` column tiles per wave,
+// one after the other (the weight is staged once for all of them).
+constexpr int kStR = 16;                       // k-steps (2 k each) per register chunk
+constexpr int kStWaves = 4;
+constexpr size_t kStMaxWeight = 64 * 1024;     // bytes of staged W^T: two workgroups per CU (160 KB of LDS)
+
+inline int stream_kpad(int K) { return (K + 2 * kStR - 1) / (2 * kStR) * (2 * kStR); }
+inline bool stream_fits(int M, int K) {
+  return M <= 96 && (size_t)stream_kpad(K) * ((M + 31) / 32 * 32) * sizeof(float) <= kStMaxWeight;
+}
+
+template <int MT, int PRE, bool GATE>
+__global__ __launch_bounds__(64 * kStWaves) void conv1x1_stream_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ in_bias, const float* __restrict__ gate, const float* __restrict__ residual,
+    float* __restrict__ y, int M, int K, int HW, int n_total, FastDiv by_hw, int act, int tiles) {
+  constexpr int NT = 64 * kStWaves, LDW = 32 * MT;
+  extern __shared__ float4 st_lds[];
+  const int Kpad = (K + 2 * kStR - 1) / (2 * kStR) * (2 * kStR);
+  float* ws = reinterpret_cast<float*>(st_lds);  // [Kpad][LDW]: W^T
+  float* bs = ws + Kpad * LDW;                   // [Kpad]: in_bias (PRE only)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = lane >> 5, l32 = lane & 31;
+  const long long khw = (long long)K * HW;
+  const int n_chunks = Kpad / (2 * kStR);
+  const int n0 = blockIdx.x * (32 * kStWaves * tiles);
+
+  int col0 = 0;            // first column of this wave's current tile
+  bool ok = false;         // this lane's column is inside B * HW
+  const float* xsrc = x;   // this lane's column, row `half`
+  const float* gsrc = x;
+  auto enter_tile = [&](int tile) {
+    col0 = n0 + tile * 32;
+    const int col = col0 + l32;
+    ok = col < n_total;
+    const unsigned b = ok ? fastdiv((unsigned)col, by_hw) : 0u;
+    xsrc = x + (long long)b * khw + (long long)half * HW + (ok ? col - (int)b * HW : 0);
+    if constexpr (GATE) gsrc = gate + (long long)b * K + half;
+  };
+
+  float xa[kStR], xb[kStR], ga[kStR], gb[kStR];
+  auto load_chunk = [&](int c, float (&xr)[kStR], float (&gr)[kStR]) {
+#pragma unroll
+    for (int j = 0; j < kStR; ++j) {
+      const int kk = min(c * (2 * kStR) + 2 * j, K - 2);  // (K % 4 == 0: rows kk, kk + 1 exist)
+      xr[j] = xsrc[(long long)kk * HW];
+      if constexpr (GATE) gr[j] = gsrc[kk];
+    }
+  };
+
+  f32x16 acc[MT];
+  auto multiply_chunk = [&](int c, const float (&xr)[kStR], const float (&gr)[kStR]) {
+#pragma unroll
+    for (int j = 0; j < kStR; ++j) {
+      const int k = c * (2 * kStR) + 2 * j;
+      float v = xr[j];
+      // the epilogue of the convolution in front: K10's expression, K10's bits
+      if constexpr (PRE >= 0) v = settled(activate<PRE>(v + bs[k + half]));
+      if constexpr (GATE) v *= gr[j];  // the squeeze-excite gate: x * g rounded as torch does
+      v = (ok && k < K) ? v : 0.0f;
+      const float* wb_ = &ws[(k + half) * LDW + l32];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(v, wb_[i * 32], acc[i], 0, 0, 0);
+    }
+  };
+
+  enter_tile(wave);
+  load_chunk(0, xa, ga);  // in flight while the weight is staged
+
+  // W^T: consecutive lanes take consecutive channels (conflict-free LDS writes), four k each
+  for (int e = tid; e < (Kpad / 4) * LDW; e += NT) {
+    const int m = e % LDW, k = (e / LDW) * 4;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (m < M && k < K) t = *reinterpret_cast<const float4*>(w + (long long)m * K + k);
+    float* d = &ws[k * LDW + m];
+    d[0] = t.x; d[LDW] = t.y; d[2 * LDW] = t.z; d[3 * LDW] = t.w;
+  }
+  if constexpr (PRE >= 0)
+    for (int k = tid; k < Kpad; k += NT) bs[k] = k < K ? in_bias[k] : 0.0f;
+  __syncthreads();
+
+  for (int tile = wave;;) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+    int c = 0;
+    for (; c + 1 < n_chunks; c += 2) {
+      load_chunk(c + 1, xb, gb);
+      multiply_chunk(c, xa, ga);
+      load_chunk(c + 2, xa, ga);  // (past the last chunk: the clamped rows again, not used)
+      multiply_chunk(c + 1, xb, gb);
+    }
+    if (c < n_chunks) multiply_chunk(c, xa, ga);
+
+    // epilogue: lane holds channel m = .. + l32, positions 8 g + 4 half + 0..3 of the tile
+    auto epilogue = [&](auto act_c) {
+      constexpr int ACT = decltype(act_c)::value;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int m = i * 32 + l32;
+        if (m >= M) continue;
+        const float bm = bias[m];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int col = col0 + 8 * g + 4 * half;
+          if (col >= n_total) continue;
+          const unsigned b = fastdiv((unsigned)col, by_hw);
+          const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
+          float4 r;
+          r.x = activate<ACT>(acc[i][4 * g + 0] + bm);
+          r.y = activate<ACT>(acc[i][4 * g + 1] + bm);
+          r.z = activate<ACT>(acc[i][4 * g + 2] + bm);
+          r.w = activate<ACT>(acc[i][4 * g + 3] + bm);
+          if (residual) {  // the block's skip connection, added after the activation (K10's order)
+            const float4 q = *reinterpret_cast<const float4*>(residual + off);
+            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+          }
+          *reinterpret_cast<float4*>(y + off) = r;
+        }
+      }
+    };
+    switch (act) {
+      case kActRelu: epilogue(std::integral_constant<int, kActRelu>{}); break;
+      case kActSilu: epilogue(std::integral_constant<int, kActSilu>{}); break;
+      case kActHardswish: epilogue(std::integral_constant<int, kActHardswish>{}); break;
+      default: epilogue(std::integral_constant<int, kActNone>{}); break;
+    }
+
+    tile += kStWaves;
+    if (tile >= kStWaves * tiles) break;
+    enter_tile(tile);
+    load_chunk(0, xa, ga);
+  }
+}
+
 // The tile table.  Chosen from the shape only; see DESIGN.md section 11 for the measurements.
 //   wide  (WM 2, WN 2, FM 3, FN 2): 192 x 128 -- many output channels (expand), when it still gives
 //                                    >= 512 workgroups
@@ -354,7 +521,10 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
 //                                    workgroup per CU, 25 % slower)
 //   deepk (WAVES w, 32 w x 16, k-tiles of 32 in a ring of three): few output channels behind a long k
 //                                    loop (conv1x1_deepk_kernel above), w = 4 or 8
-enum Conv1x1Config { kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2, kCfgDeepK = 3, kCfgCount = 4 };
+//   stream(4 waves, each 32 t x 32 columns and all of M <= 96): the whole weight in LDS, x straight from global
+//                                    memory into the MFMA operand (conv1x1_stream_kernel above); a shape whose
+//                                    weight does not fit resolves to tall
+enum Conv1x1Config { kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2, kCfgDeepK = 3, kCfgStream = 4, kCfgCount = 5 };
 
 struct Conv1x1Plan { int cfg, waves_m, bm, bn; };
 
@@ -367,9 +537,21 @@ inline Conv1x1Plan plan_deepk(int M) {
   return {kCfgDeepK, w, 32 * w, kDkBN};
 }
 
+// waves_m: the 32-row tiles every wave holds; bn: 128 columns per pass, two passes per workgroup where that still
+// leaves 1024 workgroups (one round of four per CU), so the weight is staged half as often
+inline Conv1x1Plan plan_stream(int M, int K, int HW, long long B) {
+  if (!stream_fits(M, K)) return plan_tall(M);
+  const int t = (B * HW + 127) / 128 >= 2048 ? 2 : 1;
+  return {kCfgStream, (M + 31) / 32, (M + 31) / 32 * 32, 32 * kStWaves * t};
+}
+
 inline Conv1x1Plan pick_config(int M, int K, int HW, long long B) {
   const long long n_total = B * HW;
   const long long n_tiles128 = (n_total + 127) / 128;
+  // the FusedMBConv projects on 64x64 maps (96 -> 48: 44.2 us against 52.9 on the tall tiles with the SiLU prologue,
+  // 192 -> 48: 116.0 against 119.4, batch 64, every round); 192 -> 64 and 256 -> 64 on 32x32 maps measured 3 - 5 %
+  // slower streamed and stay tall
+  if (M == 48 && K <= 192 && HW == 4096 && stream_fits(M, K)) return plan_stream(M, K, HW, B);
   if (M <= 160) return plan_tall(M);
   // project at 8x8: deep-K (960 -> 256: 30.4 us against 35.3, 1536 -> 256: 48.6 against 61.6 at batch 64); larger
   // maps keep two workgroups per 32 columns
@@ -382,7 +564,8 @@ inline Conv1x1Plan pick_config(int M, int K, int HW, long long B) {
   return {kCfgSquare, 2, 128, 128};
 }
 
-// config: -1 the library's own choice, else a Conv1x1Config forced on the shape (every one takes every shape)
+// config: -1 the library's own choice, else a Conv1x1Config forced on the shape (every one takes every shape; stream
+// where the weight does not fit LDS as tall)
 inline int plan_for(int M, int K, int HW, long long B, int config, Conv1x1Plan* p) {
   switch (config) {
     case -1: *p = pick_config(M, K, HW, B); return MTR_OK;
@@ -390,13 +573,15 @@ inline int plan_for(int M, int K, int HW, long long B, int config, Conv1x1Plan* 
     case kCfgSquare: *p = {kCfgSquare, 2, 128, 128}; return MTR_OK;
     case kCfgTall: *p = plan_tall(M); return MTR_OK;
     case kCfgDeepK: *p = plan_deepk(M); return MTR_OK;
+    case kCfgStream: *p = plan_stream(M, K, HW, B); return MTR_OK;
     default: return MTR_E_PARAM;
   }
 }
 
-template <int WM, int WN, int FM, int FN, int BK>
-static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias, const float* gate,
-                              const float* residual, float* y, int act, int M, int K, int HW,
+// PRE: the kernels' template parameter (-1: no prologue, in_bias is NULL; else the input activation's code)
+template <int WM, int WN, int FM, int FN, int BK, int PRE>
+static int launch_conv1x1_pre(const float* x, const float* w, const float* bias, const float* in_bias,
+                              const float* gate, const float* residual, float* y, int act, int M, int K, int HW,
                               long long n_total, hipStream_t stream) {
   constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
   const long long gx = (n_total + BN - 1) / BN, gy = (M + BM - 1) / BM;
@@ -404,9 +589,9 @@ static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias,
   const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WM * WN);
   const FastDiv by_hw = make_fastdiv((unsigned)HW);
   MTR_CLEAR_STALE();
-#define MTR_C1_LAUNCH(ACT)                                                                                    \
-  hipLaunchKernelGGL((conv1x1_kernel<WM, WN, FM, FN, BK, ACT>), grid, block, 0, stream, x, w, bias, gate, residual, \
-                     y, M, K, HW, (int)n_total, by_hw)
+#define MTR_C1_LAUNCH(ACT)                                                                                      \
+  hipLaunchKernelGGL((conv1x1_kernel<WM, WN, FM, FN, BK, ACT, PRE>), grid, block, 0, stream, x, w, bias, in_bias, \
+                     gate, residual, y, M, K, HW, (int)n_total, by_hw)
   switch (act) {
     case kActNone: MTR_C1_LAUNCH(kActNone); break;
     case kActRelu: MTR_C1_LAUNCH(kActRelu); break;
@@ -419,10 +604,27 @@ static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias,
   return MTR_OK;
 }
 
-template <int WAVES>
-static int launch_conv1x1_deepk(const float* x, const float* w, const float* bias, const float* gate,
-                                const float* residual, float* y, int act, int M, int K, int HW,
-                                long long n_total, hipStream_t stream) {
+template <int WM, int WN, int FM, int FN, int BK>
+static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias, const float* in_bias, int in_act,
+                              const float* gate, const float* residual, float* y, int act, int M, int K, int HW,
+                              long long n_total, hipStream_t stream) {
+#define MTR_C1_PRE(PRE) \
+  launch_conv1x1_pre<WM, WN, FM, FN, BK, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
+  switch (in_bias ? in_act : -1) {
+    case -1: return MTR_C1_PRE(-1);
+    case kActNone: return MTR_C1_PRE(kActNone);
+    case kActRelu: return MTR_C1_PRE(kActRelu);
+    case kActSilu: return MTR_C1_PRE(kActSilu);
+    case kActHardswish: return MTR_C1_PRE(kActHardswish);
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_C1_PRE
+}
+
+template <int WAVES, int PRE>
+static int launch_conv1x1_deepk_pre(const float* x, const float* w, const float* bias, const float* in_bias,
+                                    const float* gate, const float* residual, float* y, int act, int M, int K,
+                                    int HW, long long n_total, hipStream_t stream) {
   constexpr int BM = 32 * WAVES;
   constexpr size_t lds = deepk_lds_bytes(WAVES);
   const long long gx = (n_total + kDkBN - 1) / kDkBN, gy = (M + BM - 1) / BM;
@@ -432,12 +634,12 @@ static int launch_conv1x1_deepk(const float* x, const float* w, const float* bia
 #define MTR_DK_LAUNCH(ACT)                                                                                 \
   do {                                                                                                     \
     if (lds > 64 * 1024) {                                                                                 \
-      const int e = allow_dynamic_lds((const void*)conv1x1_deepk_kernel<WAVES, ACT>, lds);                 \
+      const int e = allow_dynamic_lds((const void*)conv1x1_deepk_kernel<WAVES, ACT, PRE>, lds);            \
       if (e != MTR_OK) return e;                                                                           \
     }                                                                                                      \
     MTR_CLEAR_STALE();                                                                                     \
-    hipLaunchKernelGGL((conv1x1_deepk_kernel<WAVES, ACT>), grid, block, lds, stream, x, w, bias, gate,     \
-                       residual, y, M, K, HW, (int)n_total, by_hw);                                        \
+    hipLaunchKernelGGL((conv1x1_deepk_kernel<WAVES, ACT, PRE>), grid, block, lds, stream, x, w, bias,      \
+                       in_bias, gate, residual, y, M, K, HW, (int)n_total, by_hw);                         \
   } while (0)
   switch (act) {
     case kActNone: MTR_DK_LAUNCH(kActNone); break;
@@ -449,6 +651,68 @@ static int launch_conv1x1_deepk(const float* x, const float* w, const float* bia
 #undef MTR_DK_LAUNCH
   MTR_CHECK_LAUNCH();
   return MTR_OK;
+}
+
+template <int WAVES>
+static int launch_conv1x1_deepk(const float* x, const float* w, const float* bias, const float* in_bias,
+                                int in_act, const float* gate, const float* residual, float* y, int act, int M,
+                                int K, int HW, long long n_total, hipStream_t stream) {
+#define MTR_DK_PRE(PRE) \
+  launch_conv1x1_deepk_pre<WAVES, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
+  switch (in_bias ? in_act : -1) {
+    case -1: return MTR_DK_PRE(-1);
+    case kActNone: return MTR_DK_PRE(kActNone);
+    case kActRelu: return MTR_DK_PRE(kActRelu);
+    case kActSilu: return MTR_DK_PRE(kActSilu);
+    case kActHardswish: return MTR_DK_PRE(kActHardswish);
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_DK_PRE
+}
+
+template <int MT, int PRE>
+static int launch_conv1x1_stream_pre(const float* x, const float* w, const float* bias, const float* in_bias,
+                                     const float* gate, const float* residual, float* y, int act, int M, int K,
+                                     int HW, long long n_total, int bn, hipStream_t stream) {
+  const int kpad = stream_kpad(K);
+  const size_t lds = ((size_t)kpad * 32 * MT + (PRE >= 0 ? kpad : 0)) * sizeof(float);
+  const long long gx = (n_total + bn - 1) / bn;
+  if (gx > 0x7fffffffLL) return MTR_E_SHAPE;
+  if (act < kActNone || act > kActHardswish) return MTR_E_PARAM;
+  const dim3 grid((unsigned)gx), block(64 * kStWaves);
+  const FastDiv by_hw = make_fastdiv((unsigned)HW);
+#define MTR_ST_LAUNCH(GATE)                                                                               \
+  do {                                                                                                    \
+    if (lds > 64 * 1024) {                                                                                \
+      const int e = allow_dynamic_lds((const void*)conv1x1_stream_kernel<MT, PRE, GATE>, lds);            \
+      if (e != MTR_OK) return e;                                                                          \
+    }                                                                                                     \
+    MTR_CLEAR_STALE();                                                                                    \
+    hipLaunchKernelGGL((conv1x1_stream_kernel<MT, PRE, GATE>), grid, block, lds, stream, x, w, bias,      \
+                       in_bias, gate, residual, y, M, K, HW, (int)n_total, by_hw, act,                    \
+                       bn / (32 * kStWaves));                                                             \
+  } while (0)
+  if (gate) MTR_ST_LAUNCH(true); else MTR_ST_LAUNCH(false);
+#undef MTR_ST_LAUNCH
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
+template <int MT>
+static int launch_conv1x1_stream(const float* x, const float* w, const float* bias, const float* in_bias,
+                                 int in_act, const float* gate, const float* residual, float* y, int act, int M,
+                                 int K, int HW, long long n_total, int bn, hipStream_t stream) {
+#define MTR_ST_PRE(PRE) \
+  launch_conv1x1_stream_pre<MT, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, bn, stream)
+  switch (in_bias ? in_act : -1) {
+    case -1: return MTR_ST_PRE(-1);
+    case kActNone: return MTR_ST_PRE(kActNone);
+    case kActRelu: return MTR_ST_PRE(kActRelu);
+    case kActSilu: return MTR_ST_PRE(kActSilu);
+    case kActHardswish: return MTR_ST_PRE(kActHardswish);
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_ST_PRE
 }
 
 }  // namespace mtr
@@ -466,12 +730,22 @@ extern "C" int mtr_conv1x1_plan(int M, int K, int HW, long long B, int config, i
 extern "C" int mtr_conv1x1_bias_act(const void* x, int dtype, const float* weight, const float* bias,
                                     const float* gate, const void* residual, int act, long long B, int M,
                                     int K, int HW, void* y, mtr_stream_t stream) {
-  return mtr_conv1x1_bias_act_opts(x, dtype, weight, bias, gate, residual, act, B, M, K, HW, y, stream, -1);
+  return mtr_conv1x1_bias_act_pre(x, dtype, weight, bias, nullptr, mtr::kActNone, gate, residual, act, B, M, K, HW, y,
+                                  stream, -1);
 }
 
 extern "C" int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* weight, const float* bias,
                                          const float* gate, const void* residual, int act, long long B,
                                          int M, int K, int HW, void* y, mtr_stream_t stream, int config) {
+  if (config > mtr::kCfgDeepK) return x && weight && bias && y ? MTR_E_PARAM : MTR_E_NULL;  // (stream: the _pre entry)
+  return mtr_conv1x1_bias_act_pre(x, dtype, weight, bias, nullptr, mtr::kActNone, gate, residual, act, B, M, K, HW, y,
+                                  stream, config);
+}
+
+extern "C" int mtr_conv1x1_bias_act_pre(const void* x, int dtype, const float* weight, const float* bias,
+                                        const float* in_bias, int in_act, const float* gate, const void* residual,
+                                        int act, long long B, int M, int K, int HW, void* y, mtr_stream_t stream,
+                                        int config) {
   if (!x || !weight || !bias || !y) return MTR_E_NULL;
   if (dtype != MTR_F32) return MTR_E_DTYPE;
   if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
@@ -480,7 +754,10 @@ extern "C" int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* 
   if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
     return MTR_E_SHAPE;
   if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16))
+  if (in_act < mtr::kActNone || in_act > mtr::kActHardswish) return MTR_E_PARAM;
+  if (!in_bias && in_act != mtr::kActNone) return MTR_E_PARAM;  // an input activation belongs to an input bias
+  if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
+      ((uintptr_t)in_bias % 4))
     return MTR_E_ALIGN;
   if (x == y || (residual && residual == x)) return MTR_E_PARAM;  // y is written while x is still read
   if (B == 0) return MTR_OK;
@@ -491,23 +768,31 @@ extern "C" int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* 
   hipStream_t s = (hipStream_t)stream;
   mtr::Conv1x1Plan p;
   if (mtr::plan_for(M, K, HW, B, config, &p) != MTR_OK) return MTR_E_PARAM;
+#define MTR_C1_ARGS xf, weight, bias, in_bias, in_act, gate, rf, yf, act, M, K, HW, n_total, s
+#define MTR_C1_ARGS_ST xf, weight, bias, in_bias, in_act, gate, rf, yf, act, M, K, HW, n_total, p.bn, s
   switch (p.cfg) {
-    case mtr::kCfgWide:
-      return mtr::launch_conv1x1_cfg<2, 2, 3, 2, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-    case mtr::kCfgSquare:
-      return mtr::launch_conv1x1_cfg<2, 2, 2, 2, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+    case mtr::kCfgWide: return mtr::launch_conv1x1_cfg<2, 2, 3, 2, 16>(MTR_C1_ARGS);
+    case mtr::kCfgSquare: return mtr::launch_conv1x1_cfg<2, 2, 2, 2, 16>(MTR_C1_ARGS);
+    case mtr::kCfgStream:
+      switch (p.waves_m) {
+        case 1: return mtr::launch_conv1x1_stream<1>(MTR_C1_ARGS_ST);
+        case 2: return mtr::launch_conv1x1_stream<2>(MTR_C1_ARGS_ST);
+        default: return mtr::launch_conv1x1_stream<3>(MTR_C1_ARGS_ST);
+      }
     case mtr::kCfgDeepK:
       switch (p.waves_m) {
-        case 4: return mtr::launch_conv1x1_deepk<4>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-        default: return mtr::launch_conv1x1_deepk<8>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+        case 4: return mtr::launch_conv1x1_deepk<4>(MTR_C1_ARGS);
+        default: return mtr::launch_conv1x1_deepk<8>(MTR_C1_ARGS);
       }
     default:
       switch (p.waves_m) {
-        case 1: return mtr::launch_conv1x1_cfg<1, 1, 1, 1, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-        case 2: return mtr::launch_conv1x1_cfg<2, 1, 1, 1, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-        case 3: return mtr::launch_conv1x1_cfg<3, 1, 1, 1, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-        case 4: return mtr::launch_conv1x1_cfg<4, 1, 1, 1, 32>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
-        default: return mtr::launch_conv1x1_cfg<5, 1, 1, 1, 16>(xf, weight, bias, gate, rf, yf, act, M, K, HW, n_total, s);
+        case 1: return mtr::launch_conv1x1_cfg<1, 1, 1, 1, 16>(MTR_C1_ARGS);
+        case 2: return mtr::launch_conv1x1_cfg<2, 1, 1, 1, 16>(MTR_C1_ARGS);
+        case 3: return mtr::launch_conv1x1_cfg<3, 1, 1, 1, 16>(MTR_C1_ARGS);
+        case 4: return mtr::launch_conv1x1_cfg<4, 1, 1, 1, 32>(MTR_C1_ARGS);
+        default: return mtr::launch_conv1x1_cfg<5, 1, 1, 1, 16>(MTR_C1_ARGS);
       }
   }
+#undef MTR_C1_ARGS
+#undef MTR_C1_ARGS_ST
 }

@@ -702,12 +702,13 @@ def conv1x1_supported(x, weight):
             and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
 
 
-CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3}
+CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3, 'stream': 4}
 
 
 def conv1x1_plan(M, K, HW, B, config='auto'):
     """(configuration name, waves along the channels, channels per workgroup, columns per workgroup) K13 runs a
-    shape with: the library's own choice, or what a forced `config` resolves to.  Host only."""
+    shape with: the library's own choice, or what a forced `config` resolves to ('stream' on a shape whose weight does
+    not fit LDS: 'tall').  Host only."""
     import ctypes
     plan = (ctypes.c_int * 4)()
     check(_lib.load().mtr_conv1x1_plan(M, K, HW, B, CONV1X1_CONFIGS[config], ctypes.addressof(plan)),
@@ -716,13 +717,16 @@ def conv1x1_plan(M, K, HW, B, config='auto'):
     return names[plan[0]], plan[1], plan[2], plan[3]
 
 
-def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config='auto'):
+def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config='auto', in_bias=None, in_act=None):
     """y = act(conv1x1(x * gate[:, :, None, None], w) + bias) (+ residual) in one launch on the current
     stream: x [B, K, H, W] f32 NCHW-contiguous, w [M, K] (or the [M, K, 1, 1] conv weight), bias [M],
     gate [B, K] f32 or None, residual [B, M, H, W] or None.  Stride 1, no padding; an f32 MFMA GEMM
     in a fixed k order (the same bits on every call and graph replay, and for every `config`: a key of
-    CONV1X1_CONFIGS, 'auto' the library's own choice)."""
-    require_cuda(x, w, bias, gate, residual)
+    CONV1X1_CONFIGS, 'auto' the library's own choice).
+    in_bias [K] f32 (with in_act, a key of ACT_CODES): x comes from a convolution whose epilogue was left out, and
+    every element enters the GEMM as in_act(x + in_bias[k]) (then * gate) -- the bits of
+    conv1x1_bias_act(bias_act_(x, in_bias, in_act), ...) without that pass over x, which stays untouched."""
+    require_cuda(x, w, bias, gate, residual, in_bias)
     B, K, H, W = x.shape
     M = w.shape[0]
     w = w.reshape(M, -1)
@@ -730,6 +734,10 @@ def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config
         raise ValueError(f'conv1x1_bias_act: weight has {w.shape[1]} input channels, x has {K}')
     if gate is not None and (gate.dtype != torch.float32 or gate.numel() != B * K):
         raise ValueError('conv1x1_bias_act: gate must be [B, Cin] f32')
+    if in_bias is None and in_act is not None:
+        raise ValueError('conv1x1_bias_act: in_act needs in_bias')
+    if in_bias is not None and (in_bias.dtype != torch.float32 or in_bias.numel() != K):
+        raise ValueError('conv1x1_bias_act: in_bias must be [Cin] f32')
     if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
                                  or not residual.is_contiguous()):
         raise ValueError('conv1x1_bias_act: residual must be [B, Cout, H, W] like the output, contiguous')
@@ -737,11 +745,12 @@ def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config
         out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
     elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
         raise ValueError('conv1x1_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
-    check(_lib.load().mtr_conv1x1_bias_act_opts(
+    check(_lib.load().mtr_conv1x1_bias_act_pre(
         _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
+        None if in_bias is None else _ptr(in_bias.contiguous()), ACT_CODES[in_act],
         None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
         ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device), CONV1X1_CONFIGS[config]),
-        'mtr_conv1x1_bias_act_opts')
+        'mtr_conv1x1_bias_act_pre')
     return out
 
 

@@ -16,7 +16,9 @@ last; `report` names each kernel's role in its block (SE fc1 / bias / act, fc2, 
 K10, K11, se_gate, ...) from that module and the kernel's name and writes a markdown table: per MBConv
 block the time of every role, the sum of the squeeze-excite tail, per project shape the GEMM time, and per
 depthwise layer (k, C, map, stride) its convolution kernel + K10, or K11 / K15 (`record --no-k15`: the 5x5
-layers folded as before K15).  The block tables are EfficientNetV2's; other backbones (`--backbone mobilenetv3
+layers folded as before K15; `record --no-k13-pre`: the K10 pass behind the dense 3x3 layers of stages 2 - 3, which
+the f32 copy otherwise leaves to the project's K13 launch, so that the K10 column of those blocks is empty).  The
+block tables are EfficientNetV2's; other backbones (`--backbone mobilenetv3
 --batch 320`: configs[3]) get the depthwise table and the split by kernel kind.
 Marker kernels and the gaps they open are not counted; kernel durations are the tracer's.
 `record --precision` picks the arithmetic: f32 (the default, as above), f16-autocast / bf16-autocast (the f32
@@ -45,6 +47,9 @@ def record(args):
     import bench
     from metrabs_amd.backbones import (ConvBiasAct, DepthwiseBiasAct, DepthwiseConv2d, build_backbone,
                                        calibrate_batchnorm, fold_batchnorm)
+    if args.no_k13_pre:   # the armed FusedMBConv blocks of the f32 copy on the chain: K10 behind every dense 3x3
+        from metrabs_amd.backbones import FusedMBConv
+        FusedMBConv.use_k13_pre = False
     if args.no_k15:   # the module tree from before K15: 5x5 depthwise layers as DepthwiseConv2d + K10
         DepthwiseBiasAct.kernel_sizes = (3,)
     dev = torch.device('cuda')
@@ -350,6 +355,9 @@ def main():
                    help='fold with fuse_blocks=True (a -copy precision only): the armed FusedMBConv blocks on K16h')
     r.add_argument('--fuse-stem', action='store_true',
                    help='fold with fuse_stem=True: Preproc + the stem convolution + its epilogue on K17')
+    r.add_argument('--no-k13-pre', action='store_true',
+                   help='FusedMBConv.use_k13_pre = False: the f32 copy keeps the K10 pass behind the dense 3x3 layers of '
+                        'stages 2 - 3 instead of leaving it to the project (K13 with the input prologue)')
     r.add_argument('--no-k15', action='store_true',
                    help='fold with DepthwiseBiasAct.kernel_sizes = (3,): 5x5 depthwise layers on DepthwiseConv2d + K10')
     r.add_argument('--precision', default='f32',

@@ -16,6 +16,10 @@ MI355X, 6.29 TB/s; the spec is 8.0).
 GPU time without the host's launch cost, as the estimator runs its graphed batches.  --timing eager (the f32
 default) times the calls as they are issued.  The library arm of a 16-bit run is unpinned (cudnn deterministic
 off), as the 16-bit copy runs by default; the f32 arm keeps the deterministic pin the f32 model runs under.
+The projects of the FusedMBConv blocks an f32 copy arms (FusedMBConv.pre_pair: the dense 3x3 in front leaves its K10
+pass to them) are timed as that hand-over: old = K10 in place on the expanded activation, then K13; new = K13 with
+the input prologue (in_bias, in_act), one launch and one read and one write of the activation less.  --only-pre
+times these classes alone.
 """
 import argparse
 import json
@@ -31,13 +35,15 @@ def shape_classes(batch, res, backbone='effnetv2-s'):
     from metrabs_amd import backbones
     net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True).cuda()
     out = {}
+    pre_of = {m.pre_pair[1]: m.pre_pair[0] for m in net.modules()
+              if isinstance(m, backbones.FusedMBConv) and m.pre_pair}
     for name, m in net.named_modules():
         if isinstance(m, backbones.ConvBiasAct) and m.conv.kernel_size == (1, 1) and m.conv.stride == (1, 1):
             def hook(mod, args, kwargs, name=name):
                 x = args[0]
                 gated = any(mod in se.gate_to for se in net.modules() if isinstance(se, backbones.SqueezeExcite))
                 key = (x.shape[1], mod.conv.out_channels, x.shape[2], x.shape[3], mod.act_name,
-                       kwargs.get('residual') is not None, gated)
+                       kwargs.get('residual') is not None, gated, pre_of[mod].act_name if mod in pre_of else False)
                 out.setdefault(key, []).append(name)
             m.register_forward_pre_hook(hook, with_kwargs=True)
     backbones.ConvBiasAct.use_k13 = False
@@ -57,8 +63,11 @@ def main():
     ap.add_argument('--backbone', default='effnetv2-s')
     ap.add_argument('--timing', choices=['graph', 'eager'], default=None,
                     help='default: graph for f16 / bf16, eager for f32')
-    ap.add_argument('--config', default='auto', help='f32: K13 configurations to time, comma-separated')
+    ap.add_argument('--config', default='auto', help='f32: K13 configurations to time, comma-separated; the first is the "new" arm, each further one is '
+                         'timed beside it and compared with it round by round (--config tall,stream: the streaming '
+                         'configuration against the tall tiles)')
     ap.add_argument('--max-hw', type=int, default=None)
+    ap.add_argument('--only-pre', action='store_true', help='the FusedMBConv projects that take the prologue only')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -74,8 +83,11 @@ def main():
     rows = []
     configs = args.config.split(',') if dt == torch.float32 else ['auto']
     g = torch.Generator(device='cuda').manual_seed(0)
-    for (K, M, H, W, act, res, gated), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+    for (K, M, H, W, act, res, gated, pre_act), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
         if args.max_hw is not None and H * W > args.max_hw:
+            continue
+        pre = pre_act is not False and dt == torch.float32
+        if args.only_pre and not pre:
             continue
         B = args.batch
         x = torch.randn(B, K, H, W, device='cuda', generator=g).to(dt)
@@ -84,8 +96,12 @@ def main():
         gate = torch.rand(B, K, device='cuda', generator=g) if gated else None
         r = torch.randn(B, M, H, W, device='cuda', generator=g).to(dt) if res else None
         y = torch.empty(B, M, H, W, device='cuda', dtype=dt)
+        b_in = torch.randn(K, device='cuda', generator=g) if pre else None
 
         def old():
+            if pre:   # (K10 works in place: the values of x change from call to call, the time does not)
+                kernels.bias_act_(x, b_in, pre_act)
+                return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y)
             xi = x if gate is None else x * gate.to(dt).view(B, K, 1, 1)
             yy = F.conv2d(xi, w)
             kernels.bias_act_(yy, b, act, r)
@@ -94,7 +110,8 @@ def main():
         def new(config=configs[0]):
             if dt != torch.float32:
                 return kernels.conv1x1_bias_act16(x, w, b, act, gate=gate, residual=r, out=y)
-            return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y, config=config)
+            return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y, config=config, in_bias=b_in,
+                                            in_act=pre_act if pre else None)
 
         extra = {c: (lambda c=c: new(c)) for c in configs[1:]}
 
@@ -126,7 +143,14 @@ def main():
             return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
 
         with torch.inference_mode(), torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=pinned):
-            a, c = old(), new()
+            if pre:
+                x0 = x.clone()
+                c = new().clone()
+                a = old().clone()
+                assert torch.equal(a, c)   # the prologue has K10's bits
+                x.copy_(x0)
+            else:
+                a, c = old(), new()
             torch.cuda.synchronize()
             diff = float((a - c).abs().max().float() / a.abs().max().float().clamp_min(1e-30))
             for fn in extra.values():
@@ -151,7 +175,12 @@ def main():
         byts = x.element_size() * (B * H * W * (K + M * (2 if res else 1)) + M * K)
         byte_floor = byts / (HBM_TBS * 1e12) * 1e6
         floor = max(flop / (peak * 1e12) * 1e6, byte_floor)
+        # (the old arm of a prologue class reads and writes x once more)
+        byts_old = byts + (x.element_size() * 2 * B * K * H * W if pre else 0)
         row = dict(cin=K, cout=M, hw=f'{H}x{W}', act=act, skip=res, gate=gated, layers=len(names), first=names[0],
+                   **(dict(pre_act=pre_act, old='k10+k13', old_floor_us=round(byts_old / (HBM_TBS * 1e12) * 1e6, 2),
+                           old_rounds=[round(v, 2) for v in t_old], new_rounds=[round(v, 2) for v in t_new])
+                      if pre else {}),
                    old_us=round(med(t_old), 2), **{f'{k}_us': round(med(t_new), 2),
                                                    f'{k}_tflops': round(flop / med(t_new) / 1e6, 1),
                                                    f'{k}_share_of_peak': round(flop / med(t_new) / 1e6 / peak, 3)},
@@ -163,6 +192,8 @@ def main():
                 row[f'k13_{c}_us'] = round(med(v), 2)
                 row[f'k13_{c}_plan'] = list(kernels.conv1x1_plan(M, K, H * W, B, c))
                 row[f'k13_{c}_wins_every_round'] = all(n < o for n, o in zip(v, t_old))
+                row[f'k13_{c}_rounds'] = [round(t, 2) for t in v]
+                row[f'{c}_beats_{configs[0]}_every_round'] = all(n < o for n, o in zip(v, t_new))
         if dt != torch.float32:
             row.update(dtype=args.dtype, batch=B, res=args.res, timing=timing, library_pinned=pinned, hbm_tbs=HBM_TBS,
                        byte_floor_us=round(byte_floor, 2), share_of_byte_floor=round(byte_floor / med(t_new), 3))
