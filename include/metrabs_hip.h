@@ -495,6 +495,35 @@ int mtr_depthwise3x3_bias_act_padded(const void* x, int dtype, const float* weig
                                      int pad_left, int pad_bottom, int pad_right, void* y,
                                      float* row_mean, mtr_stream_t stream);
 
+/* K18 (outside the reference's hot path, like K11): the stride-1, padding-1 depthwise 3x3 layer of K11 on register
+ * blocks, for the planes K11's own block kernel refuses (it takes a plane only when W / 4 and H / 4 are powers of
+ * two and the plane has at most 64 blocks; everything else runs on its VALU-bound generic kernel).  x, y
+ * [B, C, H, W] NCHW in `dtype` (f32 / f16 / bf16), both 16-byte aligned (else MTR_E_ALIGN); weight [C, 3, 3] and
+ * bias [C] f32; W a multiple of 4, 4 <= W <= 128, 1 <= H <= 128 (H need not be a multiple of 4), B * C < 2^24
+ * (else MTR_E_SHAPE: the caller keeps K11); act as K11.  y = rnd(act(conv + bias[c])) with the BITS of K11's
+ * generic kernel: f32 accumulation from 0 over (ky, kx) with ky outer, then the bias, the activation and one
+ * rounding; row_mean (may be NULL): [B*C] f32 mean of the stored result per plane, summed in that kernel's
+ * order, so y and row_mean equal mtr_depthwise3x3_bias_act's on every plane that reaches its generic kernel.
+ * Every check is made on the host before anything is enqueued; B == 0 returns MTR_OK without a launch.  No
+ * atomics, no workspace, no allocation; only enqueues on `stream` (graph-capturable). */
+int mtr_depthwise3x3_blocks_bias_act(const void* x, int dtype, const float* weight /*[C][3][3]*/,
+                                     const float* bias, int act, long long B, int C, int H, int W, void* y,
+                                     float* row_mean /*[B*C] or NULL*/, mtr_stream_t stream);
+/* The same with the block shape chosen by the caller.  block_cols: 0 the library's choice, 4 a lane owns 4 rows
+ * x 4 columns, 8 (f16 / bf16 only, else MTR_E_PARAM; W a multiple of 8, else MTR_E_SHAPE) 4 rows x 8 columns,
+ * one 16-byte load per row; other values MTR_E_PARAM.  The bits do not depend on block_cols. */
+int mtr_depthwise3x3_blocks_bias_act_opts(const void* x, int dtype, const float* weight, const float* bias,
+                                          int act, long long B, int C, int H, int W, void* y, float* row_mean,
+                                          mtr_stream_t stream, int block_cols);
+/* Whether K18 takes a depthwise 3x3 layer given with K11's arguments, without a launch (the idiom of
+ * mtr_conv1x1_plan): MTR_OK and *block_cols = the block shape block_cols = 0 resolves to (4 or 8), or *block_cols = 0
+ * and what the entry would answer -- MTR_E_NULL without block_cols, K11's argument errors in K11's order (MTR_E_PARAM for a stride outside {1, 2} or padding
+ * outside mtr_depthwise3x3_bias_act_padded's ranges), then MTR_E_SHAPE for what K11 runs and K18 does not
+ * (stride 2, any padding other than 1 on all four sides, W % 4 != 0, H or W above 128), then MTR_E_DTYPE.  The
+ * alignment of x and y and the plane count are the entry's own checks. */
+int mtr_depthwise3x3_blocks_supported(int dtype, int H, int W, int stride, int pad_top, int pad_left,
+                                      int pad_bottom, int pad_right, int* block_cols /*[1]*/);
+
 /* K15 (outside the reference's hot path, like K10 / K11): depthwise 5x5 convolution of the backbone's
  * inference copy with the K10 epilogue in the same pass -- the 5x5 layers of MobileNetV3-Large
  * (mobilenet_v3.py:387-432) and of the EfficientNet-B family (efficientnet.py:389-395).  K11's contract:

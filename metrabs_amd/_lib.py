@@ -143,6 +143,11 @@ SIGNATURES = {
     'mtr_depthwise3x3_bias_act_padded': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                  c_void_p, c_void_p, c_void_p]),
+    'mtr_depthwise3x3_blocks_bias_act': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                                 c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mtr_depthwise3x3_blocks_bias_act_opts': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                                      c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    'mtr_depthwise3x3_blocks_supported': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'mtr_depthwise5x5_bias_act_padded': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                  c_void_p, c_void_p, c_void_p]),

@@ -653,6 +653,10 @@ class DepthwiseBiasAct(nn.Module):
     # (C, H, W, stride) of the input where K15 measured slower than PyTorch's depthwise kernel + K10: these
     # run the torch ops
     k15_slower = frozenset()
+    # K18 (fold_batchnorm(block_depthwise=True)): the class-wide switch, and the (C, H, W) of the input where K18
+    # measured slower than K11: these stay on K11
+    use_k18 = True
+    k18_slower = frozenset()
 
     def __init__(self, conv, bias, act):
         super().__init__()
@@ -667,7 +671,11 @@ class DepthwiseBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False
         self._mean = None
-        self.last_path = None  # 'k11', 'k15' or 'library': what the last forward ran (tests, A/B runs)
+        self.last_path = None  # 'k11', 'k15', 'k18' or 'library': what the last forward ran (tests, A/B runs)
+        # fold_batchnorm(block_depthwise=True) sets this on the k = 3, stride-1, padding-1 layers: they run K18 on
+        # the planes it takes and K11's block kernel refuses -- the bits of K11's generic kernel, which those planes
+        # run on otherwise
+        self.block_depthwise = False
 
     @classmethod
     def applies_to(cls, conv):
@@ -680,6 +688,15 @@ class DepthwiseBiasAct(nn.Module):
     take_mean = ConvBiasAct.take_mean
     take_mean_f32 = ConvBiasAct.take_mean_f32
 
+    def _k18_takes(self, x, kernels):
+        """An armed layer's input (cuda, contiguous, f32 / f16 / bf16) goes to K18 instead of K11."""
+        B, C, H, W = x.shape
+        return (DepthwiseBiasAct.use_k18 and not torch.is_autocast_enabled('cuda')
+                and self.stride == 1 and self.pads is None
+                and kernels.depthwise3x3_blocks_supported(x.dtype, H, W, self.stride, self.pad, x.data_ptr())
+                and not kernels.k11_takes_block_kernel(H, W) and 0 < B * C < 2 ** 24
+                and (C, H, W) not in DepthwiseBiasAct.k18_slower)
+
     def forward(self, x):
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
         ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
@@ -687,6 +704,14 @@ class DepthwiseBiasAct(nn.Module):
         if x.is_cuda and x.is_contiguous() and ow % 4 == 0 and \
                 x.dtype in (torch.float32, torch.float16, torch.bfloat16):
             from . import kernels
+            if self.k == 3 and self.block_depthwise and self._k18_takes(x, kernels):
+                self.last_path = 'k18'
+                if self.emit_mean:
+                    y, mean = kernels.depthwise3x3_blocks_bias_act(x, self.weight, self.bias, self.act_name,
+                                                                   want_mean=True)
+                    self._mean = (y, mean)
+                    return y
+                return kernels.depthwise3x3_blocks_bias_act(x, self.weight, self.bias, self.act_name)
             if self.k == 3:
                 fn, self.last_path = kernels.depthwise3x3_bias_act, 'k11'
             elif (x.shape[1], x.shape[2], x.shape[3], self.stride) not in DepthwiseBiasAct.k15_slower and \
@@ -723,7 +748,8 @@ def _block_plus_skip(block, x):
     return x + block(x)
 
 
-def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False):
+def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
+                   block_depthwise=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -750,7 +776,13 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     -- the first dense 3x3 stride-2 padding-1 Cin = 3 ConvBiasAct -- a StemConvBiasAct, which runs Preproc, the
     convolution and its epilogue as ONE launch (K17) where that kernel takes the input and the library chain
     everywhere else, and arms the Preproc directly in front of it to hand its input over untouched.  The
-    state_dict keys are those of the copy without the option."""
+    state_dict keys are those of the copy without the option.
+    block_depthwise=True (needs fused_epilogue=True; any dtype; off by default; independent of the other options)
+    arms every 3x3, stride-1, padding-1 DepthwiseBiasAct without a folded ZeroPad2d: such a layer runs K18, the
+    register-block kernel, on the planes that kernel takes and K11's own block kernel refuses (24x24 and 12x12 of
+    EfficientNetV2 at 384 px, 128x128 and 64x64 of MobileNetV3 at 256 px), and K11 everywhere else.  K18 returns
+    the bits of K11's generic kernel for the output and the mean, so the armed copy's features are torch.equal to
+    the default copy's.  A plain attribute on the layers: no module, buffer or state_dict key is added."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -763,6 +795,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: fuse_blocks=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
     if fuse_stem and not fused_epilogue:
         raise ValueError('fold_batchnorm: fuse_stem=True needs fused_epilogue=True')
+    if block_depthwise and not fused_epilogue:
+        raise ValueError('fold_batchnorm: block_depthwise=True needs fused_epilogue=True')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -847,6 +881,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                         and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
                         and last[0].conv.in_channels == first[0].conv.out_channels:
                     m.fused_pair = (first[0], last[0])
+    if block_depthwise:  # depthwise 3x3 stride 1 padding 1: K18 where K11 would take its generic kernel
+        for m in folded.modules():
+            if isinstance(m, DepthwiseBiasAct) and m.k == 3 and m.stride == 1 and m.pad == 1 and m.pads is None:
+                m.block_depthwise = True
     if fuse_stem:  # Preproc -> stem 3x3 stride 2: one launch (K17)
         stem_blk = next((m for m in folded.modules() if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct
                          and not m[0].emit_mean and StemConvBiasAct.applies_to(m[0].conv)), None)

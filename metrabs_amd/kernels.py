@@ -628,6 +628,66 @@ def depthwise3x3_bias_act(x, weight, bias, act, stride, pad, want_mean=False):
     return (y, mean) if want_mean else y
 
 
+# K18: the stride-1, padding-1 depthwise 3x3 layer on register blocks (csrc/depthwise3x3_blocks.hip)
+
+def k11_takes_block_kernel(H, W):
+    """Whether K11 (depthwise3x3_bias_act at stride 1, padding 1, on a 16-byte aligned x of fewer than 2^24
+    planes) runs an [.., H, W] plane on its stride-1 block kernel instead of its generic kernel: launch_depthwise's
+    condition in csrc/depthwise.hip, restated.  W / 4 and H / 4 powers of two, at most 16 blocks per row and 64
+    per plane."""
+    if H <= 0 or W <= 0 or H % 4 or W % 4:
+        return False
+    bw, bh = W // 4, H // 4
+    if bw & (bw - 1) or bh & (bh - 1):
+        return False
+    return bw <= 16 and bw * bh <= 64
+
+
+def depthwise3x3_blocks_supported(dtype, H, W, stride=1, pad=1, data_ptr=0):
+    """Whether K18 takes a depthwise 3x3 layer on [.., H, W] planes of `dtype`: stride 1, zero padding 1 on all four
+    sides (pad: an int or (left, right, top, bottom) like torch.nn.ZeroPad2d), W a multiple of 4 up to 128, H up to
+    128, f32 / f16 / bf16, and -- where the tensor's data_ptr() is given -- a 16-byte aligned base.  Host only; the
+    rules of mtr_depthwise3x3_blocks_supported, restated (a test holds the two together)."""
+    pl, pr, pt, pb = (pad,) * 4 if isinstance(pad, int) else tuple(int(p) for p in pad)
+    return (dtype in (torch.float32, torch.float16, torch.bfloat16) and stride == 1
+            and (pl, pr, pt, pb) == (1, 1, 1, 1) and 1 <= H <= 128 and 4 <= W <= 128 and W % 4 == 0
+            and data_ptr % 16 == 0)
+
+
+def depthwise3x3_blocks_plan(dtype, H, W):
+    """The block shape (4 or 8 columns of a lane's 4-row block) K18's own choice resolves to for [.., H, W] planes of
+    `dtype`, or None where the kernel does not take them.  Host only (mtr_depthwise3x3_blocks_supported)."""
+    import ctypes
+    cols = ctypes.c_int(0)
+    rc = _lib.load().mtr_depthwise3x3_blocks_supported(dtype_code(dtype), int(H), int(W), 1, 1, 1, 1, 1,
+                                                       ctypes.addressof(cols))
+    return cols.value if rc == 0 else None
+
+
+def depthwise3x3_blocks_bias_act(x, weight, bias, act, want_mean=False, block_cols=None):
+    """K18: y = act(depthwise_conv3x3(x, weight) + bias) at stride 1 and zero padding 1 in one pass over register
+    blocks (+ the [B, C] f32 mean of y over H*W if want_mean), with the bits of depthwise3x3_bias_act's generic
+    kernel for y and the mean.  x NCHW-contiguous f32 / f16 / bf16, 16-byte aligned, W % 4 == 0, H and W at most
+    128; weight [C, 1, 3, 3] or [C, 3, 3].  block_cols: None the library's choice, 4 or 8 (f16 / bf16 with
+    W % 8 == 0) columns of a lane's 4-row block; the bits do not depend on it.  What the kernel does not take
+    raises (depthwise3x3_blocks_supported asks first); there is no fallback in here."""
+    require_cuda(x, weight, bias)
+    if not x.is_contiguous():
+        raise ValueError('depthwise3x3_blocks_bias_act needs an NCHW-contiguous tensor')
+    if weight.numel() != x.shape[1] * 9:
+        raise ValueError(f'depthwise3x3_blocks_bias_act needs a [C, 3, 3] weight, got {tuple(weight.shape)}')
+    if block_cols not in (None, 4, 8):
+        raise ValueError(f'depthwise3x3_blocks_bias_act: block_cols must be None, 4 or 8, got {block_cols}')
+    B, C, H, W = x.shape
+    y = torch.empty(B, C, H, W, device=x.device, dtype=x.dtype)
+    mean = torch.empty(B, C, device=x.device, dtype=torch.float32) if want_mean else None
+    check(_lib.load().mtr_depthwise3x3_blocks_bias_act_opts(
+        _ptr(x), dtype_code(x.dtype), _ptr(weight.contiguous().float()), _ptr(bias.contiguous().float()),
+        ACT_CODES[act], B, C, H, W, _ptr(y), None if mean is None else _ptr(mean),
+        current_stream_ptr(x.device), int(block_cols or 0)), 'mtr_depthwise3x3_blocks_bias_act_opts')
+    return (y, mean) if want_mean else y
+
+
 def depthwise5x5_supported(H, W, pad):
     """Whether K15 takes an [.., H, W] plane with padding `pad` (an int or (left, right, top, bottom)): the
     padded plane is staged through LDS and may be at most 112 x 112 (csrc/depthwise5x5.hip)."""

@@ -55,7 +55,7 @@ def load_joint_info(model_dir):
 
 
 def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
-                    fuse_blocks=False, fuse_stem=False):
+                    fuse_blocks=False, fuse_stem=False, block_depthwise=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
@@ -67,7 +67,10 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     (backbones.fold_batchnorm(fuse_blocks=True), K16h): the same bits, off by default.
     fuse_stem=True (off by default) runs Preproc and the stem convolution of the copy as one launch
     (backbones.fold_batchnorm(fuse_stem=True), K17).  It works with every dtype -- an f32 copy gets the f32 kernel --
-    and always gives the folded copy with fused epilogues, whatever fold_batchnorm and fused_epilogue say."""
+    and always gives the folded copy with fused epilogues, whatever fold_batchnorm and fused_epilogue say.
+    block_depthwise=True (off by default) runs the copy's stride-1 depthwise 3x3 layers on K18 where K11 would take
+    its generic kernel (backbones.fold_batchnorm(block_depthwise=True)): the same bits.  Like fuse_stem it works with
+    every dtype and always gives the folded copy with fused epilogues."""
     if dtype == torch.float32:
         dtype = None
     if dtype not in (None, torch.float16, torch.bfloat16):
@@ -93,10 +96,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     if dtype is not None:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype, fuse_blocks=fuse_blocks,
-                              fuse_stem=fuse_stem)
-    elif fuse_stem:
+                              fuse_stem=fuse_stem, block_depthwise=block_depthwise)
+    elif fuse_stem or block_depthwise:
         from .backbones import fold_batchnorm as fold
-        model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=True)
+        model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=fuse_stem,
+                              block_depthwise=block_depthwise)
     elif fold_batchnorm:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=fused_epilogue)
@@ -104,11 +108,12 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
 
 
 def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchnorm=False,
-                           fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False):
-    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem: as load_crop_model (a
-    16-bit copy also makes the estimator sample 16-bit crops)."""
+                           fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
+                           block_depthwise=False):
+    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise: as
+    load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
     model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
-                            fuse_blocks=fuse_blocks, fuse_stem=fuse_stem)
+                            fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

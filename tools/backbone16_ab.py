@@ -21,6 +21,9 @@ rows carry ab='k16h'.
 --ab k17: both arms are the same copy of the same network (16-bit, or f32 with --dtype f32; --config 1, 3 or 4), A
 folded as by default, B with fuse_stem=True (Preproc + the stem convolution + its epilogue as one launch, K17).  The
 rows carry ab='k17'.
+--ab k18: both arms are the same copy of the same network (16-bit, or f32 with --dtype f32; --config 3 or 4), A folded
+as by default, B with block_depthwise=True (the stride-1 depthwise 3x3 layers on K18 where K11 would take its generic
+kernel).  The arms return the same poses bit for bit.  The rows carry ab='k18'.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -40,13 +43,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18'], default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
-                         "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem")
+                         "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
+                         "k18: without vs with block_depthwise")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17'):
-        ap.error('--dtype f32 and --config 3 go with --ab k15 or --ab k17')
+    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18'):
+        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17 or --ab k18')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -79,6 +83,15 @@ def main():
             if dt is None:
                 e.crop_model.autocast_dtype = None               # f32 copies, run in f32
         assert any(isinstance(m, StemConvBiasAct) for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k18':                                         # both arms the same copy, B with K18 armed
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   block_depthwise=True)
+        for e in (est_a, est_b):
+            e.crop_dtype = e.crop_model.input_dtype
+            if dt is None:
+                e.crop_model.autocast_dtype = None               # f32 copies, run in f32
+        assert any(isinstance(m, DepthwiseBiasAct) and m.block_depthwise for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -155,6 +168,14 @@ def main():
         from metrabs_amd.backbones import StemConvBiasAct
         row = dict(kind='paths', ab='k17', stem=[m.last_path for m in est_b.crop_model.backbone.modules()
                                                   if isinstance(m, StemConvBiasAct)])
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k18':
+        paths = [[m.last_path for m in e.crop_model.backbone.modules() if isinstance(m, DepthwiseBiasAct) and m.k == 3]
+                 for e in (est_a, est_b)]
+        row = dict(kind='paths', ab='k18', equal_poses=bool(torch.equal(p_a, p_b)),
+                   a={k: paths[0].count(k) for k in sorted(set(paths[0]))},
+                   b={k: paths[1].count(k) for k in sorted(set(paths[1]))})
         print(json.dumps(row), flush=True)
         rows.append(row)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -62,7 +62,7 @@ def record(args):
                         samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
                          dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
-                         fuse_stem=args.fuse_stem)
+                         fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
         x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
@@ -142,6 +142,8 @@ def _kind(kname):
         return 'K10'
     if 'depthwise5x5' in k:
         return 'K15'
+    if 'depthwise3x3_blocks' in k:  # K18 (before K11's match): the stride-1 layers on register blocks
+        return 'K18'
     if 'depthwise3x3' in k:
         return 'K11'
     if 'depthwise' in k:  # PyTorch's own depthwise kernel (conv_depthwise2d_forward_kernel)
@@ -165,7 +167,7 @@ def _role(module, kind):
     """Role of a kernel inside its MBConv block from the module that launched it and its kind."""
     parts = module.split('.')
     last = parts[-1]
-    if kind in ('K10', 'K11', 'se_gate'):
+    if kind in ('K10', 'K11', 'K18', 'se_gate'):
         return kind
     if last == 'fc1':
         return 'SE fc1' if kind == 'gemm' else 'SE fc1 bias'
@@ -234,15 +236,15 @@ def _fused_table(per_kernel, pat):
 
 def _depthwise_table(per_kernel, depthwise, total):
     """Every depthwise layer: k, C, input map, stride, then what served it -- PyTorch's depthwise kernel (or MIOpen)
-    + K10, or the one-pass K11 / K15."""
+    + K10, or the one-pass K11 / K18 / K15."""
     if not depthwise:
         return []
-    cols = ['conv', 'K10', 'K11', 'K15', 'other']
+    cols = ['conv', 'K10', 'K11', 'K18', 'K15', 'other']
     rows = OrderedDict((n, defaultdict(float)) for n in depthwise)
     for module, kind, kname, us in per_kernel:
         for n in depthwise:
             if module == n or module.startswith(n + '.'):
-                col = kind if kind in ('K10', 'K11', 'K15') else 'conv' if kind in ('dw conv', 'conv') else 'other'
+                col = kind if kind in ('K10', 'K11', 'K18', 'K15') else 'conv' if kind in ('dw conv', 'conv') else 'other'
                 rows[n][col] += us
                 break
     lines = ['', '## Depthwise layers', '',
@@ -296,7 +298,7 @@ def report(args):
             if role == 'project' and kind in ('gemm', 'conv', 'K13', 'K13h'):
                 # (K13 runs inside the ConvBiasAct, the library GEMM inside its .conv)
                 proj[tuple(convs.get(module) or convs.get(module + '.conv', ('?',)))].append(us)
-            role = role if kind in ('gemm', 'conv', 'K11', 'K13', 'K13h') else f'{role} {kind}'
+            role = role if kind in ('gemm', 'conv', 'K11', 'K18', 'K13', 'K13h') else f'{role} {kind}'
         b[role] += us
     tail_roles = ['SE fc1', 'SE fc1 bias', 'SE act', 'SE fc2', 'SE fc2 bias', 'SE gate fn', 'se_gate', 'x * gate',
                   'project', 'K10']
@@ -355,6 +357,9 @@ def main():
                    help='fold with fuse_blocks=True (a -copy precision only): the armed FusedMBConv blocks on K16h')
     r.add_argument('--fuse-stem', action='store_true',
                    help='fold with fuse_stem=True: Preproc + the stem convolution + its epilogue on K17')
+    r.add_argument('--block-depthwise', action='store_true',
+                   help='fold with block_depthwise=True: the stride-1 depthwise 3x3 layers on K18 where K11 would take '
+                        'its generic kernel')
     r.add_argument('--no-k13-pre', action='store_true',
                    help='FusedMBConv.use_k13_pre = False: the f32 copy keeps the K10 pass behind the dense 3x3 layers of '
                         'stages 2 - 3 instead of leaving it to the project (K13 with the input prologue)')
