@@ -620,6 +620,19 @@ int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weight, const f
                            const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
                            int M, int K, int HW, void* y, mtr_stream_t stream);
 
+/* mtr_conv1x1_bias_act16 with the tile configuration stated (tests, A/B runs, the backbone's deep projects).  config:
+ * -1 the library's own choice (exactly mtr_conv1x1_bias_act16, a pure function of (M, K)), 0 tall (32 w x 32), 1 square
+ * (128 x 128), 2 deep-K (64 x 64, x and W through LDS, three k-tiles of 64 in flight, the result stored in whole row
+ * segments); else MTR_E_PARAM.  The other argument rules are mtr_conv1x1_bias_act16's, in its order.  Every
+ * configuration takes every shape and returns the same bits. */
+int mtr_conv1x1_bias_act16_opts(const void* x, int dtype, const void* weight, const float* bias,
+                                const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
+                                int M, int K, int HW, void* y, mtr_stream_t stream, int config);
+
+/* Host only: what `config` (as above) resolves to for a shape.  plan[0 .. 3] = configuration (0 .. 2), waves along the
+ * channels, channels per workgroup, columns per workgroup. */
+int mtr_conv1x1_plan16(int M, int K, int HW, long long B, int config, int* plan /*[4]*/);
+
 /* K14h (outside the reference's hot path, like K10): a dense 3x3 convolution of f16 / bf16 tensors -- stride 1 or
  * 2, padding 1 on all sides, no dilation, groups 1 -- as one implicit 16-bit MFMA GEMM
  * (v_mfma_f32_32x32x16_{f16,bf16}) with the K10 epilogue folded in:

@@ -168,6 +168,9 @@ SIGNATURES = {
                                      ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_conv1x1_bias_act16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                        ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_conv1x1_bias_act16_opts': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                            ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    'mtr_conv1x1_plan16': (c_int, [c_int, c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
     'mtr_conv3x3_bias_act16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                        c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_conv3x3_16_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int]),

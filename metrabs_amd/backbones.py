@@ -85,7 +85,7 @@ class SqueezeExcite(nn.Module):
             g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
                                 _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)], w2t=self._fc2_wt())
             for dst in self.gate_to:
-                if dst.k13_takes(x) or dst.k13h_takes(x):
+                if dst.k13_takes(x) or dst.k13h_takes(x) or dst.k13h_deep_takes(x):
                     # the project conv (K13 / K13h) multiplies x by the gate as it stages x: no x * g pass
                     dst.give_gate(x, g)
                     return x
@@ -393,7 +393,8 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        # 'k13', 'k13_gate', 'k13h', 'k13h_gate' or 'library': what the last forward ran (tests, A/B runs)
+        # 'k13', 'k13_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate' or 'library': what the last forward ran
+        # (tests, A/B runs)
         self.last_path = None
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
@@ -436,6 +437,9 @@ class ConvBiasAct(nn.Module):
         """Whether forward(x) runs on K13h (conv1x1_16.hip): a 1x1 stride-1 unpadded ungrouped conv of a 16-bit
         copy (fold_batchnorm(dtype=)) on a CUDA NCHW-contiguous input of the copy's dtype, autocast off, no
         gradient wanted, a shape the C entry accepts."""
+        return self._k13h_takes(x, ConvBiasAct.k13h_slower)
+
+    def _k13h_takes(self, x, slower):
         c = self.conv
         if not (ConvBiasAct.use_k13h and not self.emit_mean and x.is_cuda and x.dtype == c.weight.dtype
                 and x.dtype in (torch.float16, torch.bfloat16) and c.kernel_size == (1, 1)
@@ -444,10 +448,25 @@ class ConvBiasAct(nn.Module):
             return False
         if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
             return False
-        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k13h_slower:
+        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in slower:
             return False
         from . import kernels
         return kernels.conv1x1_16_supported(x, c.weight)
+
+    # fold_batchnorm(deep_projects=True) sets this on the deep project convolutions of a 16-bit copy (1x1, stride 1,
+    # ungrouped, no activation, Cin >= 768, Cout > 160): they run K13h in `deep_config` wherever K13h takes the input,
+    # the shapes of k13h_slower included
+    deep_projects = False
+    # the K13h configuration of an armed layer (tests and A/B runs set 'auto': the same layers on K13h's old tiles)
+    deep_config = 'deepk'
+    # (Cin, Cout, H * W) where K13h 'deepk' did not beat the library path an armed layer would otherwise take in every
+    # round (EfficientNetV2-L, batch 32, 384 px): these keep today's branch
+    k13h_deep_slower = frozenset({(3840, 640, 144)})
+
+    def k13h_deep_takes(self, x):
+        """Whether forward(x) runs on K13h in `deep_config`: an armed layer on an input k13h_takes would accept apart
+        from the k13h_slower list, unless its shape is in k13h_deep_slower."""
+        return self.deep_projects and self._k13h_takes(x, ConvBiasAct.k13h_deep_slower)
 
     def give_gate(self, x, gate):
         """Hands over the squeeze-excite gate [B, C] f32 of `x`: the next forward(x) applies it."""
@@ -483,8 +502,14 @@ class ConvBiasAct(nn.Module):
         w16 = self.conv.weight.dtype
         if x.dtype != w16 and w16 in (torch.float16, torch.bfloat16) and not torch.is_autocast_enabled(x.device.type):
             x = x.to(w16)  # the first convolution of a 16-bit copy: the input is cast once, here
-        if self.k13h_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                                        and residual.data_ptr() % 16 == 0)):
+        skip_ok = residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                       and residual.data_ptr() % 16 == 0)
+        if skip_ok and self.k13h_deep_takes(x):
+            from . import kernels
+            self.last_path = 'k13h_deep' if gate is None else 'k13h_deep_gate'
+            return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
+                                              residual=residual, config=ConvBiasAct.deep_config)
+        if skip_ok and self.k13h_takes(x):
             from . import kernels
             self.last_path = 'k13h' if gate is None else 'k13h_gate'
             return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
@@ -749,7 +774,7 @@ def _block_plus_skip(block, x):
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                   block_depthwise=False):
+                   block_depthwise=False, deep_projects=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -782,7 +807,16 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     register-block kernel, on the planes that kernel takes and K11's own block kernel refuses (24x24 and 12x12 of
     EfficientNetV2 at 384 px, 128x128 and 64x64 of MobileNetV3 at 256 px), and K11 everywhere else.  K18 returns
     the bits of K11's generic kernel for the output and the mean, so the armed copy's features are torch.equal to
-    the default copy's.  A plain attribute on the layers: no module, buffer or state_dict key is added."""
+    the default copy's.  A plain attribute on the layers: no module, buffer or state_dict key is added.
+    deep_projects=True (needs a 16-bit dtype; off by default; independent of the other options) arms every 1x1,
+    stride-1, ungrouped ConvBiasAct without activation that has Cin >= 768 and Cout > 160 -- the deep project
+    convolutions of the MBConv tails: 15 layers of EfficientNetV2-S, 60 of EfficientNetV2-L, none of MobileNetV3 or
+    ResNet.  An armed layer runs K13h in its deep-K configuration (ConvBiasAct.deep_config, .last_path 'k13h_deep' /
+    'k13h_deep_gate') with the squeeze-excite gate and the skip folded in, wherever K13h takes the input -- the
+    shapes of ConvBiasAct.k13h_slower, which run cast + x * gate + rocBLAS + K10 by default, included -- unless the
+    shape is in ConvBiasAct.k13h_deep_slower; everything else takes today's branch.  The armed layers' results
+    differ from the library chain's by rounding (another summation order), and are the bits of K13h's other
+    configurations.  A plain attribute on the layers: no module, buffer or state_dict key is added."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -797,6 +831,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: fuse_stem=True needs fused_epilogue=True')
     if block_depthwise and not fused_epilogue:
         raise ValueError('fold_batchnorm: block_depthwise=True needs fused_epilogue=True')
+    if deep_projects and dtype is None:
+        raise ValueError('fold_batchnorm: deep_projects=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -885,6 +921,12 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         for m in folded.modules():
             if isinstance(m, DepthwiseBiasAct) and m.k == 3 and m.stride == 1 and m.pad == 1 and m.pads is None:
                 m.block_depthwise = True
+    if deep_projects:  # the deep project convolutions: K13h's deep-K configuration, the listed-slower shapes included
+        for m in folded.modules():
+            c = m.conv if type(m) is ConvBiasAct else None
+            if c is not None and m.act is None and c.kernel_size == (1, 1) and c.stride == (1, 1) \
+                    and c.padding == (0, 0) and c.groups == 1 and c.in_channels >= 768 and c.out_channels > 160:
+                m.deep_projects = True
     if fuse_stem:  # Preproc -> stem 3x3 stride 2: one launch (K17)
         stem_blk = next((m for m in folded.modules() if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct
                          and not m[0].emit_mean and StemConvBiasAct.applies_to(m[0].conv)), None)

@@ -27,6 +27,8 @@
 // current one is multiplied); rows past M, columns past B * HW and k past K are zero-filled, never stored.
 // The k order is the same in every configuration -- 16-k MFMA steps at 0, 16, 32, ... -- so the result
 // does not depend on the tile picked.  No atomics, no split-K: the same inputs give the same bits.
+#include <type_traits>
+
 #include "common.h"
 
 namespace mtr {
@@ -220,12 +222,230 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_16_kernel(
   }
 }
 
+// The deep-K configuration: a few hundred output channels behind a long k loop (the project convolutions of
+// the MBConv tails: K = 768 .. 3840).  The tiles above keep ONE k-tile of global loads in flight and read W
+// from L2 per wave; the 128 x 128 tiles leave half the CUs idle on 12x12 maps.  Here a workgroup of four
+// waves takes 64 channels x 64 columns, every wave one 32 x 32 tile -- a single accumulation chain of the
+// 32x32x16 MFMA issues back to back, so one chain per wave costs no throughput -- which gives 2 - 3 workgroups
+// per CU on those shapes.  k-tiles of 64 go global -> registers -> a ring of three LDS stages like K13's
+// deep-K: tile t + 3 is requested before tile t is multiplied and tile t + 2 (requested one whole tile
+// earlier) is written to LDS between the two halves of tile t's MFMAs.  Waves 0 and 1 stage x (transposed
+// into the X^T image as above, the gate product on the way), waves 2 and 3 stage W as it lies in memory
+// ([m][k], rows padded like the X^T image), so both MFMA operands are 16-byte LDS reads and W crosses L2
+// once per workgroup.  The loads carry no condition: walked pointers over the whole tiles, clamped addresses in the
+// tail, zero-fill on the way to LDS.  The
+// accumulators leave through LDS ([channel][position] f32), so every store instruction writes 128-byte row
+// segments and the residual is read the same way.  The same 16-k MFMA steps in the same order as every
+// other configuration, and the same epilogue expression: the same bits.
+constexpr int kDk16BM = 64, kDk16BN = 64, kDk16BK = 64, kDk16Stages = 3;
+constexpr int kDk16LDK = kDk16BK + kC16Pad;  // elements per row of the X^T and W images
+constexpr int kDk16LDY = kDk16BN + 4;        // floats per channel row of the staged result
+
+template <int DT, bool GATE>
+__global__ __launch_bounds__(256) void conv1x1_16_deepk_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ gate, const unsigned short* __restrict__ residual, unsigned short* __restrict__ y,
+    int M, int K, int HW, int n_total, FastDiv by_hw, int act) {
+  using H = Bits16<DT>;
+  constexpr int BM = kDk16BM, BN = kDk16BN, BK = kDk16BK, LDK = kDk16LDK, LDY = kDk16LDY;
+  constexpr int XS = BN * LDK, WS = BM * LDK;  // elements per stage
+  static_assert((BK / 4) * (BN / 8) == 128 && BM * (BK / 8) == 4 * 128, "loader mappings: 128 threads each");
+  static_assert(BM * LDY * 4 <= kDk16Stages * (XS + WS) * 2, "the staged result fits the ring");
+  __shared__ __attribute__((aligned(16))) unsigned short lds[kDk16Stages * (XS + WS)];
+  unsigned short* xs = lds;                     // [stage][position][LDK]
+  unsigned short* ws = lds + kDk16Stages * XS;  // [stage][channel][LDK]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const int r = lane & 31, h = lane >> 5;
+
+  // loader roles, fixed for the whole k loop (wave-uniform).  x: positions 8 p8 .. + 7, k 4 q + i of each k-tile
+  // (a wave takes 32 k: a load instruction reads whole 128-byte rows, and the 8-byte LDS writes of 16 lanes -- eight
+  // q, two p8 -- are two-way on a bank at most); W: rows q + 16 i, k 8 p8 .. + 7.  Either way four 16-byte loads at
+  // src[i] + min(k0 + kb + i * ki, kmax) * kmul.
+  const bool isx = __builtin_amdgcn_readfirstlane(tid) < 128;
+  const int p8 = isx ? (tid >> 3) & 7 : tid & 7, q = isx ? (tid & 7) | ((tid >> 6) & 1) << 3 : (tid & 127) >> 3;
+  const int xcol = n0 + 8 * p8;
+  const bool xcol_ok = xcol < n_total;
+  const unsigned xb = xcol_ok ? fastdiv((unsigned)xcol, by_hw) : 0u;
+  const unsigned short* src[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    src[i] = isx ? x + (long long)xb * K * HW + (xcol_ok ? xcol - (int)xb * HW : 0)
+                 : w + (long long)min(m0 + q + 16 * i, M - 1) * K;
+  const int kb = isx ? 4 * q : 8 * p8, ki = isx ? 1 : 0, kmax = isx ? K - 1 : K - 8, kmul = isx ? HW : 1;
+  // the gate of the x rows; the W waves read bias[0] instead (any readable float: never used)
+  const float* gsrc = GATE && isx ? gate + (long long)xb * K : bias;
+  const int gmul = GATE && isx ? 1 : 0;
+  // the main loop's loads (whole tiles: nothing to clamp) walk pointers, tile 3 first; the W waves' "gate" there is
+  // the gate row of their own column and k group, in bounds like the x waves' and as unused as bias[0]
+  const unsigned short* cur[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cur[i] = src[i] + (long long)(3 * BK + kb + i * ki) * kmul;
+  const float* gcur = GATE ? gate + (long long)xb * K + 3 * BK + 4 * q : bias;  // (q < 16 in both roles)
+  const long long adv = (long long)BK * kmul;
+
+  // Two register sets (tiles t + 2 and t + 3 are in flight together), always indexed by a constant.
+  uint4 rr[2][4];
+  float rg[2][4];
+  auto load_tile = [&](int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * BK + kb;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = min(k0 + i * ki, kmax);
+      rr[P][i] = *reinterpret_cast<const uint4*>(src[i] + k * kmul);
+      if constexpr (GATE) rg[P][i] = gsrc[k * gmul];
+    }
+  };
+  auto load_next_whole_tile = [&](auto set) {
+    constexpr int P = decltype(set)::value;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      rr[P][i] = *reinterpret_cast<const uint4*>(cur[i]);
+      if constexpr (GATE) rg[P][i] = gcur[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cur[i] += adv;
+    if constexpr (GATE) gcur += BK;
+  };
+  auto store_tile = [&](int stage, int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * BK + kb;
+    if (isx) {  // 4 k-rows x 8 positions -> 8 positions x 4 k of the X^T image
+      u16x8 xr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xr[i] = __builtin_bit_cast(u16x8, rr[P][i]);
+        if constexpr (GATE) {  // the squeeze-excite gate, once per staged element, rounded as torch's x * gate.to(x.dtype)
+          const float g = H::f32(H::rnd(rg[P][i]));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xr[i][e] = H::rnd(H::f32(xr[i][e]) * g);
+        }
+        const bool ok = xcol_ok && k0 + i < K;  // (a clamped load may give anything: selected away, never multiplied to zero)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xr[i][e] = ok ? xr[i][e] : (unsigned short)0;
+      }
+      unsigned short* xd = &xs[stage * XS + (8 * p8) * LDK + 4 * q];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        uint2 v;
+        v.x = (unsigned)xr[0][j] | ((unsigned)xr[1][j] << 16);
+        v.y = (unsigned)xr[2][j] | ((unsigned)xr[3][j] << 16);
+        *reinterpret_cast<uint2*>(xd + j * LDK) = v;
+      }
+    } else {
+      // (the gate registers count as read on this path too: a load left pending here makes the wait-count pass hold
+      // the next load into the same register back until most of the tile in flight has arrived)
+      if constexpr (GATE) asm volatile("" ::"v"(rg[P][0]), "v"(rg[P][1]), "v"(rg[P][2]), "v"(rg[P][3]));
+      const bool k_ok = k0 < K;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool ok = k_ok && m0 + q + 16 * i < M;
+        uint4 u = rr[P][i];
+        u.x = ok ? u.x : 0u; u.y = ok ? u.y : 0u; u.z = ok ? u.z : 0u; u.w = ok ? u.w : 0u;
+        *reinterpret_cast<uint4*>(&ws[stage * WS + (q + 16 * i) * LDK + 8 * p8]) = u;
+      }
+    }
+  };
+
+  c16_f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  auto multiply = [&](int stage, int s0) {
+    const unsigned short* xa = &xs[stage * XS + (wn * 32 + r) * LDK + 8 * h];
+    const unsigned short* wa = &ws[stage * WS + (wm * 32 + r) * LDK + 8 * h];
+#pragma unroll
+    for (int s = s0; s < s0 + BK / 32; ++s)
+      acc = H::mfma(*reinterpret_cast<const uint4*>(xa + 16 * s), *reinterpret_cast<const uint4*>(wa + 16 * s), acc);
+  };
+
+  const int n_tiles = (K + BK - 1) / BK;
+  constexpr std::integral_constant<int, 0> ra{};
+  constexpr std::integral_constant<int, 1> rb{};
+  load_tile(0, ra);
+  if (n_tiles > 1) load_tile(1, rb);
+  store_tile(0, 0, ra);
+  if (n_tiles > 1) store_tile(1, 1, rb);
+  if (n_tiles > 2) load_tile(2, ra);
+  __syncthreads();
+  // at the top of step t: tiles t and t + 1 are in LDS, tile t + 2 is on its way to `hold`
+  int stage = 0;
+  auto step = [&](int t, auto hold, auto issue, auto guarded) {
+    constexpr bool G = decltype(guarded)::value;
+    if constexpr (!G) load_next_whole_tile(issue);
+    else if (t + 3 < n_tiles) load_tile(t + 3, issue);
+    multiply(stage, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // stage of tile t + 2 = stage of tile t - 1: last read before the previous barrier
+    if (!G || t + 2 < n_tiles) store_tile(stage == 0 ? 2 : stage - 1, t + 2, hold);
+    __builtin_amdgcn_sched_barrier(0);
+    multiply(stage, BK / 32);
+    stage = stage == 2 ? 0 : stage + 1;
+    __syncthreads();
+  };
+  // the body of the loop has no condition around its loads; the last steps, which have, run apart
+  int t = 0;
+  for (; t + 5 < n_tiles; t += 2) {  // tiles t + 3 and t + 4 are whole: neither is the last one
+    step(t, ra, rb, std::false_type{});
+    step(t + 1, rb, ra, std::false_type{});
+  }
+  for (; t < n_tiles; t += 2) {
+    step(t, ra, rb, std::true_type{});
+    if (t + 1 < n_tiles) step(t + 1, rb, ra, std::true_type{});
+  }
+
+  // the ring is free (the barrier above): the lane's channel wm 32 + r, positions wn 32 + 8 g + 4 h + 0..3
+  float* ys = reinterpret_cast<float*>(lds);  // [channel][LDY]
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<float4*>(&ys[(wm * 32 + r) * LDY + wn * 32 + 8 * g + 4 * h]) =
+        make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+  __syncthreads();
+  // eight threads per channel row: 8 positions (16 bytes of y and of the residual) each
+  auto epilogue = [&](auto tag) {
+    constexpr int ACT = decltype(tag)::value;
+#pragma unroll
+    for (int u = 0; u < BM * (BN / 8) / 256; ++u) {
+      const int ch = (tid >> 3) + 32 * u, c8 = 8 * (tid & 7), m = m0 + ch, col = n0 + c8;
+      if (m >= M || col >= n_total) continue;
+      const float bm = bias[m];
+      const unsigned b = fastdiv((unsigned)col, by_hw);
+      const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
+      const float4 a0 = *reinterpret_cast<const float4*>(&ys[ch * LDY + c8]);
+      const float4 a1 = *reinterpret_cast<const float4*>(&ys[ch * LDY + c8 + 4]);
+      float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = activate<ACT>(v[e] + bm);
+      if (residual) {  // the block's skip connection, added after the activation (K10's order)
+        const u16x8 q8 = __builtin_bit_cast(u16x8, *reinterpret_cast<const uint4*>(residual + off));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += H::f32(q8[e]);
+      }
+      u16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = H::rnd(v[e]);
+      *reinterpret_cast<uint4*>(y + off) = __builtin_bit_cast(uint4, o);
+    }
+  };
+  switch (act) {
+    case kActRelu: epilogue(ActTag<kActRelu>()); break;
+    case kActSilu: epilogue(ActTag<kActSilu>()); break;
+    case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
+    default: epilogue(ActTag<kActNone>()); break;
+  }
+}
+
 // The tile table, chosen from the shape only:
 //   tall  (WM w, WN 1, FM 1, FN 1, BK 64): 32 w x 32, w = ceil(M / 32) <= 5 -- few output channels (the
 //          project convs): the whole of M in one workgroup, every position read once
 //   tall4 at M = 256, K >= 512 (8x8 projects): two workgroups of 4 waves per 32 columns
 //   square(WM 2, WN 2, FM 2, FN 2, BK 32): 128 x 128 -- many output channels (expand, head)
-enum Conv1x1Config16 { kCfg16Tall = 0, kCfg16Square = 1 };
+//   deepk (2 x 2 waves of one 32 x 32 tile, BK 64 in a ring of three): 64 x 64 -- a few hundred output channels
+//          behind a long k loop (conv1x1_16_deepk_kernel above); never the library's own choice, asked for by
+//          mtr_conv1x1_bias_act16_opts
+enum Conv1x1Config16 { kCfg16Tall = 0, kCfg16Square = 1, kCfg16DeepK = 2 };
 
 struct Conv1x1Plan16 { int cfg, waves_m; };
 
@@ -233,6 +453,18 @@ inline Conv1x1Plan16 pick_config16(int M, int K) {
   if (M <= 160) return {kCfg16Tall, (M + 31) / 32};
   if (M == 256 && K >= 512) return {kCfg16Tall, 4};
   return {kCfg16Square, 2};
+}
+
+// config: -1 the library's own choice, else a Conv1x1Config16 forced on the shape (every one takes every shape; tall
+// past 160 channels as rows of 128-channel workgroups)
+inline int plan_for16(int M, int K, int config, Conv1x1Plan16* p) {
+  switch (config) {
+    case -1: *p = pick_config16(M, K); return MTR_OK;
+    case kCfg16Tall: *p = {kCfg16Tall, M <= 160 ? (M + 31) / 32 : 4}; return MTR_OK;
+    case kCfg16Square: *p = {kCfg16Square, 2}; return MTR_OK;
+    case kCfg16DeepK: *p = {kCfg16DeepK, kDk16BM / 32}; return MTR_OK;
+    default: return MTR_E_PARAM;
+  }
 }
 
 template <int DT, int WM, int WN, int FM, int FN, int BK>
@@ -253,9 +485,31 @@ static int launch_conv1x1_16_cfg(const void* x, const void* w, const float* bias
 }
 
 template <int DT>
+static int launch_conv1x1_16_deepk(const void* x, const void* w, const float* bias, const float* gate,
+                                   const void* residual, void* y, int act, int M, int K, int HW, long long n_total,
+                                   hipStream_t stream) {
+  const long long gx = (n_total + kDk16BN - 1) / kDk16BN, gy = (M + kDk16BM - 1) / kDk16BM;
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  const dim3 grid((unsigned)gx, (unsigned)gy), block(256);
+  const FastDiv by_hw = make_fastdiv((unsigned)HW);
+  MTR_CLEAR_STALE();
+#define MTR_DK16_LAUNCH(GATE)                                                                                        \
+  hipLaunchKernelGGL((conv1x1_16_deepk_kernel<DT, GATE>), grid, block, 0, stream, (const unsigned short*)x,          \
+                     (const unsigned short*)w, bias, gate, (const unsigned short*)residual, (unsigned short*)y, M, K, \
+                     HW, (int)n_total, by_hw, act)
+  if (gate) MTR_DK16_LAUNCH(true); else MTR_DK16_LAUNCH(false);
+#undef MTR_DK16_LAUNCH
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
+template <int DT>
 static int launch_conv1x1_16(const void* x, const void* w, const float* bias, const float* gate, const void* residual,
-                             void* y, int act, int M, int K, int HW, long long n_total, hipStream_t s) {
-  const Conv1x1Plan16 p = pick_config16(M, K);
+                             void* y, int act, int M, int K, int HW, long long n_total, int config, hipStream_t s) {
+  Conv1x1Plan16 p;
+  if (plan_for16(M, K, config, &p) != MTR_OK) return MTR_E_PARAM;
+  if (p.cfg == kCfg16DeepK)
+    return launch_conv1x1_16_deepk<DT>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
   if (p.cfg == kCfg16Square)
     return launch_conv1x1_16_cfg<DT, 2, 2, 2, 2, 32>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
   switch (p.waves_m) {
@@ -269,9 +523,28 @@ static int launch_conv1x1_16(const void* x, const void* w, const float* bias, co
 
 }  // namespace mtr
 
+extern "C" int mtr_conv1x1_plan16(int M, int K, int HW, long long B, int config, int* plan) {
+  if (!plan) return MTR_E_NULL;
+  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
+  mtr::Conv1x1Plan16 p;
+  const int e = mtr::plan_for16(M, K, config, &p);
+  if (e != MTR_OK) return e;
+  plan[0] = p.cfg;
+  plan[1] = p.waves_m;
+  plan[2] = p.cfg == mtr::kCfg16Square ? 128 : 32 * p.waves_m;
+  plan[3] = p.cfg == mtr::kCfg16Square ? 128 : p.cfg == mtr::kCfg16DeepK ? mtr::kDk16BN : 32;
+  return MTR_OK;
+}
+
 extern "C" int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weight, const float* bias,
                                       const float* gate, const void* residual, int act, long long B, int M, int K,
                                       int HW, void* y, mtr_stream_t stream) {
+  return mtr_conv1x1_bias_act16_opts(x, dtype, weight, bias, gate, residual, act, B, M, K, HW, y, stream, -1);
+}
+
+extern "C" int mtr_conv1x1_bias_act16_opts(const void* x, int dtype, const void* weight, const float* bias,
+                                           const float* gate, const void* residual, int act, long long B, int M,
+                                           int K, int HW, void* y, mtr_stream_t stream, int config) {
   if (!x || !weight || !bias || !y) return MTR_E_NULL;
   if (dtype != MTR_F16 && dtype != MTR_BF16) return MTR_E_DTYPE;
   if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
@@ -280,6 +553,7 @@ extern "C" int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weig
   if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
     return MTR_E_SHAPE;
   if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
+  if (config < -1 || config > mtr::kCfg16DeepK) return MTR_E_PARAM;
   if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
       ((uintptr_t)bias % 4) || ((uintptr_t)gate % 4))
     return MTR_E_ALIGN;
@@ -287,6 +561,6 @@ extern "C" int mtr_conv1x1_bias_act16(const void* x, int dtype, const void* weig
   if (B == 0) return MTR_OK;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == MTR_F16)
-    return mtr::launch_conv1x1_16<MTR_F16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, s);
-  return mtr::launch_conv1x1_16<MTR_BF16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, s);
+    return mtr::launch_conv1x1_16<MTR_F16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, config, s);
+  return mtr::launch_conv1x1_16<MTR_BF16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, config, s);
 }

@@ -829,13 +829,28 @@ def conv1x1_16_supported(x, weight):
             and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
 
 
-def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None):
+CONV1X1_16_CONFIGS = {'auto': -1, 'tall': 0, 'square': 1, 'deepk': 2}
+
+
+def conv1x1_16_plan(M, K, HW, B, config='auto'):
+    """(configuration name, waves along the channels, channels per workgroup, columns per workgroup) K13h runs a
+    shape with: the library's own choice, or what a forced `config` resolves to.  Host only."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    check(_lib.load().mtr_conv1x1_plan16(M, K, HW, B, CONV1X1_16_CONFIGS[config], ctypes.addressof(plan)),
+          'mtr_conv1x1_plan16')
+    names = {v: k for k, v in CONV1X1_16_CONFIGS.items()}
+    return names[plan[0]], plan[1], plan[2], plan[3]
+
+
+def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None, config='auto'):
     """y = act(conv1x1(x * gate.to(x.dtype)[:, :, None, None], w) + bias) (+ residual) in one launch on the
     current stream, for f16 / bf16: x [B, K, H, W] NCHW-contiguous, w [M, K] (or the [M, K, 1, 1] conv weight)
     in x's dtype, bias [M] f32, gate [B, K] f32 or None, residual [B, M, H, W] in x's dtype or None.  Stride 1,
     no padding; f32 accumulation in a fixed k order, rounded to x's dtype once (the same bits on every call
-    and graph replay)."""
+    and graph replay, and for every `config`: a key of CONV1X1_16_CONFIGS, 'auto' the library's own choice)."""
     require_cuda(x, w, bias, gate, residual)
+    code = CONV1X1_16_CONFIGS[config]
     B, K, H, W = x.shape
     M = w.shape[0]
     w = w.reshape(M, -1)
@@ -852,10 +867,13 @@ def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None):
         out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
     elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
         raise ValueError('conv1x1_bias_act16: out must be [B, Cout, H, W] like the output, contiguous')
-    check(_lib.load().mtr_conv1x1_bias_act16(
-        _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
-        None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
-        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act16')
+    args = (_ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
+            None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
+            ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device))
+    if code < 0:  # today's call
+        check(_lib.load().mtr_conv1x1_bias_act16(*args), 'mtr_conv1x1_bias_act16')
+    else:
+        check(_lib.load().mtr_conv1x1_bias_act16_opts(*args, code), 'mtr_conv1x1_bias_act16_opts')
     return out
 
 

@@ -55,7 +55,7 @@ def load_joint_info(model_dir):
 
 
 def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
-                    fuse_blocks=False, fuse_stem=False, block_depthwise=False):
+                    fuse_blocks=False, fuse_stem=False, block_depthwise=False, deep_projects=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
@@ -70,7 +70,10 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     and always gives the folded copy with fused epilogues, whatever fold_batchnorm and fused_epilogue say.
     block_depthwise=True (off by default) runs the copy's stride-1 depthwise 3x3 layers on K18 where K11 would take
     its generic kernel (backbones.fold_batchnorm(block_depthwise=True)): the same bits.  Like fuse_stem it works with
-    every dtype and always gives the folded copy with fused epilogues."""
+    every dtype and always gives the folded copy with fused epilogues.
+    deep_projects=True (a 16-bit dtype only, else ValueError; off by default) runs the copy's deep project
+    convolutions on K13h's deep-K configuration with the squeeze-excite gate and the skip folded in
+    (backbones.fold_batchnorm(deep_projects=True)): equal to the default copy up to rounding."""
     if dtype == torch.float32:
         dtype = None
     if dtype not in (None, torch.float16, torch.bfloat16):
@@ -78,6 +81,8 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
                          f'got {dtype}')
     if fuse_blocks and dtype is None:
         raise ValueError('load_crop_model: fuse_blocks=True needs dtype=torch.float16 or torch.bfloat16')
+    if deep_projects and dtype is None:
+        raise ValueError('load_crop_model: deep_projects=True needs dtype=torch.float16 or torch.bfloat16')
     cfg, raw = load_config(model_dir)
     # config.affine_weights (models/metrabs.py:23-32) is a path or a name under $DATA_ROOT/skeleton_conversion;
     # a file of that name shipped INSIDE the model directory is found too
@@ -96,7 +101,7 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     if dtype is not None:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype, fuse_blocks=fuse_blocks,
-                              fuse_stem=fuse_stem, block_depthwise=block_depthwise)
+                              fuse_stem=fuse_stem, block_depthwise=block_depthwise, deep_projects=deep_projects)
     elif fuse_stem or block_depthwise:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=fuse_stem,
@@ -109,11 +114,12 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
 
 def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchnorm=False,
                            fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                           block_depthwise=False):
-    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise: as
-    load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
+                           block_depthwise=False, deep_projects=False):
+    """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise, deep_projects:
+    as load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
     model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
-                            fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise)
+                            fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
+                            deep_projects=deep_projects)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

@@ -24,6 +24,9 @@ rows carry ab='k17'.
 --ab k18: both arms are the same copy of the same network (16-bit, or f32 with --dtype f32; --config 3 or 4), A folded
 as by default, B with block_depthwise=True (the stride-1 depthwise 3x3 layers on K18 where K11 would take its generic
 kernel).  The arms return the same poses bit for bit.  The rows carry ab='k18'.
+--ab deepk: both arms are the 16-bit copy of the same network (--config 1 or 4), A folded as by default, B with
+deep_projects=True (the deep project convolutions on K13h's deep-K configuration instead of cast + x * gate + rocBLAS +
+K10).  The arms differ by rounding; the rows carry ab='deepk' and the paths of the armed layers.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -43,10 +46,10 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk'], default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
-                         "k18: without vs with block_depthwise")
+                         "k18: without vs with block_depthwise; deepk: without vs with deep_projects")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18'):
@@ -55,7 +58,7 @@ def main():
     import numpy as np
     import torch
     import bench
-    from metrabs_amd.backbones import Conv3x3BiasAct, DepthwiseBiasAct, fold_batchnorm
+    from metrabs_amd.backbones import Conv3x3BiasAct, ConvBiasAct, DepthwiseBiasAct, fold_batchnorm
     dt = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': None}[args.dtype]
     argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype]
     bargs = bench.parse_args()
@@ -92,6 +95,12 @@ def main():
             if dt is None:
                 e.crop_model.autocast_dtype = None               # f32 copies, run in f32
         assert any(isinstance(m, DepthwiseBiasAct) and m.block_depthwise for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'deepk':                                       # both arms the 16-bit copy, B with its deep projects armed
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   deep_projects=True)
+        assert any(isinstance(m, ConvBiasAct) and m.deep_projects for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -175,6 +184,14 @@ def main():
                  for e in (est_a, est_b)]
         row = dict(kind='paths', ab='k18', equal_poses=bool(torch.equal(p_a, p_b)),
                    a={k: paths[0].count(k) for k in sorted(set(paths[0]))},
+                   b={k: paths[1].count(k) for k in sorted(set(paths[1]))})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'deepk':
+        paths = [[m.last_path for m in e.crop_model.backbone.modules() if isinstance(m, ConvBiasAct)
+                  and (m.act is None and m.conv.in_channels >= 768 and m.conv.out_channels > 160
+                       and m.conv.kernel_size == (1, 1))] for e in (est_a, est_b)]
+        row = dict(kind='paths', ab='deepk', a={k: paths[0].count(k) for k in sorted(set(paths[0]))},
                    b={k: paths[1].count(k) for k in sorted(set(paths[1]))})
         print(json.dumps(row), flush=True)
         rows.append(row)

@@ -24,7 +24,9 @@ Marker kernels and the gaps they open are not counted; kernel durations are the 
 `record --precision` picks the arithmetic: f32 (the default, as above), f16-autocast / bf16-autocast (the f32
 copy under torch.autocast, 16-bit crops: bench.py's --precision f16 / bf16), f16-copy / bf16-copy (the 16-bit
 copy, fold_batchnorm(dtype=), 16-bit crops; unpinned like 16-bit autocast); `--backbone` / `--batch` / `--res`
-the network and shape (effnetv2-l, 32, 384: configs[4]).
+the network and shape (effnetv2-l, 32, 384: configs[4]); `record --deep-projects` folds a -copy precision with
+deep_projects=True (the deep project convolutions on K13h's deep-K configuration: their x * gate, gemm, K10 and cast
+columns are empty).
 """
 import argparse
 import contextlib
@@ -62,7 +64,8 @@ def record(args):
                         samples=bench.synthetic_crops(types.SimpleNamespace(res=args.res, num_aug=1), dev))
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
                          dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
-                         fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise)
+                         fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise,
+                         deep_projects=args.deep_projects)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
         x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
@@ -134,7 +137,7 @@ def _kind(kname):
         return 'K16h'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
         return 'K14h'
-    if 'conv1x1_16_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
+    if 'conv1x1_16_kernel' in k or 'conv1x1_16_deepk_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
         return 'K13h'
     if 'conv1x1_kernel' in k:  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
         return 'K13'
@@ -360,6 +363,9 @@ def main():
     r.add_argument('--block-depthwise', action='store_true',
                    help='fold with block_depthwise=True: the stride-1 depthwise 3x3 layers on K18 where K11 would take '
                         'its generic kernel')
+    r.add_argument('--deep-projects', action='store_true',
+                   help='fold with deep_projects=True (a -copy precision only): the deep project convolutions on '
+                        "K13h's deep-K configuration")
     r.add_argument('--no-k13-pre', action='store_true',
                    help='FusedMBConv.use_k13_pre = False: the f32 copy keeps the K10 pass behind the dense 3x3 layers of '
                         'stages 2 - 3 instead of leaving it to the project (K13 with the input prologue)')

@@ -12,6 +12,9 @@ gate) is timed with device events over --iters calls per arm, the two arms alter
 reported as the median per-call time with its share of the MFMA peak (155 TF f32, 2.5 PF f16 / bf16) and of
 the HBM floor (one read of x, w and the skip, one write of y, at HBM_TBS: the measured copy bandwidth of an
 MI355X, 6.29 TB/s; the spec is 8.0).
+--config lists the configurations to time (f32: kernels.CONV1X1_CONFIGS, 16 bits: kernels.CONV1X1_16_CONFIGS); --deep
+keeps the deep project classes only (no activation, Cin >= 768, Cout > 160: what fold_batchnorm(deep_projects=True)
+arms), e.g. --dtype f16 --deep --config deepk,auto: the library chain, K13h 'deepk' and K13h's own choice.
 --timing graph (the 16-bit default) captures --iters calls of each arm in a HIP graph and times its replays:
 GPU time without the host's launch cost, as the estimator runs its graphed batches.  --timing eager (the f32
 default) times the calls as they are issued.  The library arm of a 16-bit run is unpinned (cudnn deterministic
@@ -63,11 +66,12 @@ def main():
     ap.add_argument('--backbone', default='effnetv2-s')
     ap.add_argument('--timing', choices=['graph', 'eager'], default=None,
                     help='default: graph for f16 / bf16, eager for f32')
-    ap.add_argument('--config', default='auto', help='f32: K13 configurations to time, comma-separated; the first is the "new" arm, each further one is '
+    ap.add_argument('--config', default='auto', help='K13 / K13h configurations to time, comma-separated; the first is the "new" arm, each further one is '
                          'timed beside it and compared with it round by round (--config tall,stream: the streaming '
                          'configuration against the tall tiles)')
     ap.add_argument('--max-hw', type=int, default=None)
     ap.add_argument('--only-pre', action='store_true', help='the FusedMBConv projects that take the prologue only')
+    ap.add_argument('--deep', action='store_true', help='the deep project classes only (no activation, Cin >= 768, Cout > 160)')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -81,13 +85,15 @@ def main():
     timing = args.timing or ('eager' if dt == torch.float32 else 'graph')
     pinned = dt == torch.float32
     rows = []
-    configs = args.config.split(',') if dt == torch.float32 else ['auto']
+    configs = args.config.split(',')
     g = torch.Generator(device='cuda').manual_seed(0)
     for (K, M, H, W, act, res, gated, pre_act), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
         if args.max_hw is not None and H * W > args.max_hw:
             continue
         pre = pre_act is not False and dt == torch.float32
         if args.only_pre and not pre:
+            continue
+        if args.deep and not (act is None and K >= 768 and M > 160):
             continue
         B = args.batch
         x = torch.randn(B, K, H, W, device='cuda', generator=g).to(dt)
@@ -109,7 +115,7 @@ def main():
 
         def new(config=configs[0]):
             if dt != torch.float32:
-                return kernels.conv1x1_bias_act16(x, w, b, act, gate=gate, residual=r, out=y)
+                return kernels.conv1x1_bias_act16(x, w, b, act, gate=gate, residual=r, out=y, config=config)
             return kernels.conv1x1_bias_act(x, w, b, act, gate=gate, residual=r, out=y, config=config, in_bias=b_in,
                                             in_act=pre_act if pre else None)
 
@@ -185,14 +191,17 @@ def main():
                                                    f'{k}_tflops': round(flop / med(t_new) / 1e6, 1),
                                                    f'{k}_share_of_peak': round(flop / med(t_new) / 1e6 / peak, 3)},
                    floor_us=round(floor, 2), speedup=round(med(t_old) / med(t_new), 3), rel_diff=diff)
-        if dt == torch.float32:
-            row.update(config=configs[0], plan=list(kernels.conv1x1_plan(M, K, H * W, B, configs[0])), timing=timing,
+        plan = kernels.conv1x1_plan if dt == torch.float32 else kernels.conv1x1_16_plan
+        if dt == torch.float32 or args.config != 'auto':
+            row.update(config=configs[0], plan=list(plan(M, K, H * W, B, configs[0])), timing=timing,
                        wins_every_round=all(n < o for n, o in zip(t_new, t_old)))
+            if dt != torch.float32:
+                row.update(old_rounds=[round(v, 2) for v in t_old], new_rounds=[round(v, 2) for v in t_new])
             for c, v in t_extra.items():
-                row[f'k13_{c}_us'] = round(med(v), 2)
-                row[f'k13_{c}_plan'] = list(kernels.conv1x1_plan(M, K, H * W, B, c))
-                row[f'k13_{c}_wins_every_round'] = all(n < o for n, o in zip(v, t_old))
-                row[f'k13_{c}_rounds'] = [round(t, 2) for t in v]
+                row[f'{k}_{c}_us'] = round(med(v), 2)
+                row[f'{k}_{c}_plan'] = list(plan(M, K, H * W, B, c))
+                row[f'{k}_{c}_wins_every_round'] = all(n < o for n, o in zip(v, t_old))
+                row[f'{k}_{c}_rounds'] = [round(t, 2) for t in v]
                 row[f'{c}_beats_{configs[0]}_every_round'] = all(n < o for n, o in zip(v, t_new))
         if dt != torch.float32:
             row.update(dtype=args.dtype, batch=B, res=args.res, timing=timing, library_pinned=pinned, hbm_tbs=HBM_TBS,
