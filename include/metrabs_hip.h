@@ -593,17 +593,18 @@ int mtr_conv1x1_bias_act_opts(const void* x, int dtype, const float* weight, con
  * so mtr_bias_act_nchw(x, in_bias, in_act) followed by mtr_conv1x1_bias_act_opts(x, ...) gives the same bits, with
  * one read and one write of x less.  in_bias [K] f32 (4-byte aligned, else MTR_E_ALIGN) or NULL: no prologue, and
  * in_act must then be 0 (else MTR_E_PARAM).  in_act: as `act`.  Everything else as mtr_conv1x1_bias_act_opts, and
- * one more configuration: 4 stream (four waves, each 32 columns and all of M <= 96 channels; the whole weight staged
+ * two more configurations: 4 stream (four waves, each 32 columns and all of M <= 96 channels; the whole weight staged
  * in LDS once, at most 64 KiB of it, x read straight into the MFMA operand).  Forced on a shape whose weight does not
- * fit, it runs as tall.  The same bits as every other configuration. */
+ * fit, it runs as tall.  5 deep64 (eight waves on 64 channels x 64 columns, three k-tiles of 32 in flight in a ring
+ * of LDS stages); takes every shape.  The same bits as every other configuration. */
 int mtr_conv1x1_bias_act_pre(const void* x, int dtype, const float* weight, const float* bias,
                              const float* in_bias /*[K] or NULL*/, int in_act, const float* gate /*[B*K] or NULL*/,
                              const void* residual, int act, long long B, int M, int K, int HW, void* y,
                              mtr_stream_t stream, int config);
 
-/* Host only: what `config` (as above, 4 stream included) resolves to for a shape.  plan[0 .. 3] = configuration
- * (0 .. 4; 2 for stream where the weight does not fit), waves along the channels (stream: 32-channel tiles per wave),
- * channels per workgroup, columns per workgroup. */
+/* Host only: what `config` (as above, 4 stream and 5 deep64 included) resolves to for a shape.  plan[0 .. 3] =
+ * configuration (0 .. 5; 2 for stream where the weight does not fit), waves along the channels (stream: 32-channel
+ * tiles per wave; deep64: 2, of 2 x 4 waves), channels per workgroup, columns per workgroup. */
 int mtr_conv1x1_plan(int M, int K, int HW, long long B, int config, int* plan /*[4]*/);
 
 /* K13h (outside the reference's hot path, like K10): mtr_conv1x1_bias_act for f16 / bf16 tensors, one 16-bit

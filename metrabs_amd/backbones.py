@@ -400,8 +400,9 @@ class ConvBiasAct(nn.Module):
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
     use_k13 = True
     # (Cin, Cout, H * W) where K13 measured slower than rocBLAS + K10 (+ x * gate) at the bench shape
-    # (EfficientNetV2-S, batch 64, 256 px; DESIGN.md sections 11 and 15): these stay on the library path
-    k13_slower = frozenset({(1536, 256, 64)})
+    # (EfficientNetV2-S, batch 64, 256 px; DESIGN.md sections 11 and 15): these stay on the library path.  Empty
+    # since 1536 -> 256 on 8x8 maps runs K13's 'deep64' tiles
+    k13_slower = frozenset()
 
     def k13_takes(self, x):
         """Whether forward(x) runs on K13 (conv1x1.hip): a 1x1 stride-1 unpadded ungrouped conv on an f32

@@ -362,6 +362,185 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
   }
 }
 
+// The 64 x 64 ring-staged configuration ('deep64'): the deep-K pipeline above on a tile that re-reads half as much.
+// deep-K's 256 x 16 tile reads the whole of W once per 16 columns (1536 -> 256 on 8x8 maps at batch 64: 400 MB of W
+// from L2 per layer); here a workgroup of eight waves takes 64 channels x 64 columns, every wave 32 channels x 16
+// columns on v_mfma_f32_16x16x4_f32 (two independent accumulators: the MFMA issues every 32 cycles, a dependent one
+// after 40), two waves per SIMD on a CU that holds one workgroup.  k-tiles of 32 go global -> registers -> a ring of
+// three LDS stages exactly as above: tile t + 3 is requested before tile t is multiplied, tile t + 2 is written to
+// LDS between the halves of tile t's MFMAs, one barrier per tile behind MFMAs.  Every thread stages ONE 16-byte group
+// of x and ONE of W per tile.  W lies in LDS as in memory ([m][k], rows 34 floats apart, two 8-byte writes per
+// group: the fragment reads of 16 rows x 2 k per half-wave hit 32 distinct banks), x as [k][64] with the 16-column
+// groups of odd k rows swapped in pairs (the fragment reads of 2 k x 16 columns per half-wave hit 32 distinct banks
+// without a pad).  16.5 KB per stage, 49.5 KB in all: three workgroups per CU on the larger maps.
+// The loads carry no condition and no arithmetic: pointers walked by one tile over the whole tiles, clamped addresses
+// in the last steps; the zero-fill, the prologue and the gate product are applied on the way to LDS (a zero-filled
+// entry is selected, so it stays zero).  Each lane ends with four consecutive positions of one channel, a wave's
+// store instruction writes 64-byte row segments.  The k order is 0, 1, 2, ... as everywhere: the same bits.
+constexpr int kD6BM = 64, kD6BN = 64, kD6BK = 32, kD6Stages = 3, kD6Waves = 8;
+constexpr int kD6LDW = kD6BK + 2;
+
+template <int ACT, int PRE>
+__global__ __launch_bounds__(64 * kD6Waves) void conv1x1_deep64_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ in_bias, const float* __restrict__ gate, const float* __restrict__ residual,
+    float* __restrict__ y, int M, int K, int HW, int n_total, FastDiv by_hw) {
+  constexpr int NT = 64 * kD6Waves, BM = kD6BM, BN = kD6BN, BK = kD6BK, LDW = kD6LDW;
+  constexpr int XS = BK * BN, WS = BM * LDW;  // floats per stage
+  static_assert(BK * (BN / 4) == NT && BM * (BK / 4) == NT, "loader mappings: one 16-byte group of x and of W each");
+  __shared__ __attribute__((aligned(16))) float d6_lds[kD6Stages * (XS + WS)];
+  float* xs = d6_lds;                   // [stage][k][64], columns ^ 16 in odd rows
+  float* ws = d6_lds + kD6Stages * XS;  // [stage][m][LDW]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const long long khw = (long long)K * HW;
+
+  // x: every thread one k row and four consecutive columns of the 32 x 64 tile, fixed for the whole k loop
+  const int xn4 = tid & 15, xk = tid >> 4;
+  const int xcol = n0 + 4 * xn4;
+  const bool xcol_ok = xcol < n_total;
+  const unsigned xb = xcol_ok ? fastdiv((unsigned)xcol, by_hw) : 0u;
+  const float* xsrc = xcol_ok ? x + (long long)xb * khw + (xcol - (int)xb * HW) : x;
+  const bool has_gate = gate != nullptr;
+  const float* gsrc = has_gate ? gate + (long long)xb * K : x;  // (no gate: any K readable floats, multiplied by 1)
+  const int xdst = xk * BN + ((4 * xn4) ^ ((xk & 1) << 4));
+  // W: every thread one row and four consecutive k of the 64 x 32 tile
+  const int wk4 = tid & 7, wr = tid >> 3;
+  const float* wsrc = w + (long long)min(m0 + wr, M - 1) * K;
+  const bool wrow_ok = m0 + wr < M;
+  const int wdst = wr * LDW + 4 * wk4;
+  // the main loop's loads (whole tiles: nothing to clamp) walk pointers, tile 3 first
+  const float* xcur = xsrc + (long long)(3 * BK + xk) * HW;
+  const float* gcur = gsrc + 3 * BK + xk;
+  const float* bcur = PRE >= 0 ? in_bias + 3 * BK + xk : nullptr;
+  const float* wcur = wsrc + 3 * BK + 4 * wk4;
+  const long long xadv = (long long)BK * HW;
+
+  // Two register sets (tiles t + 2 and t + 3 are in flight together), always indexed by a constant.
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 rx[2] = {zero, zero}, rw[2] = {zero, zero};
+  float rg[2] = {1.0f, 1.0f}, rbi[2] = {0.0f, 0.0f};
+  auto load_tile = [&](int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * BK;
+    const int kx = min(k0 + xk, K - 1);
+    rx[P] = *reinterpret_cast<const float4*>(xsrc + (long long)kx * HW);
+    rg[P] = gsrc[kx];
+    if constexpr (PRE >= 0) rbi[P] = in_bias[kx];
+    rw[P] = *reinterpret_cast<const float4*>(wsrc + min(k0 + 4 * wk4, K - 4));
+  };
+  auto load_next_whole_tile = [&](auto set) {
+    constexpr int P = decltype(set)::value;
+    rx[P] = *reinterpret_cast<const float4*>(xcur);
+    rg[P] = *gcur;
+    if constexpr (PRE >= 0) rbi[P] = *bcur;
+    rw[P] = *reinterpret_cast<const float4*>(wcur);
+    xcur += xadv; gcur += BK; wcur += BK;
+    if constexpr (PRE >= 0) bcur += BK;
+  };
+  auto store_tile = [&](int stage, int kt, auto set) {
+    constexpr int P = decltype(set)::value;
+    const int k0 = kt * BK;
+    const float g = has_gate ? rg[P] : 1.0f;  // the squeeze-excite gate, once per staged element: x * g rounded as torch does
+    const bool x_ok = xcol_ok && k0 + xk < K;
+    float4 v = rx[P];
+    if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits.  A clamped
+      // load may give anything here (inf, NaN): it is selected away below, never multiplied to zero
+      const float bi = rbi[P];
+      v.x = settled(activate<PRE>(v.x + bi)); v.y = settled(activate<PRE>(v.y + bi));
+      v.z = settled(activate<PRE>(v.z + bi)); v.w = settled(activate<PRE>(v.w + bi));
+    }
+    v.x = x_ok ? v.x * g : 0.0f; v.y = x_ok ? v.y * g : 0.0f; v.z = x_ok ? v.z * g : 0.0f; v.w = x_ok ? v.w * g : 0.0f;
+    *reinterpret_cast<float4*>(&xs[stage * XS + xdst]) = v;
+    const bool ok = wrow_ok && k0 + 4 * wk4 < K;  // (selects of scalars: a select of two float4 objects goes through memory)
+    const float4 u = rw[P];
+    float* wd = &ws[stage * WS + wdst];
+    *reinterpret_cast<float2*>(wd) = make_float2(ok ? u.x : 0.0f, ok ? u.y : 0.0f);
+    *reinterpret_cast<float2*>(wd + 2) = make_float2(ok ? u.z : 0.0f, ok ? u.w : 0.0f);
+  };
+
+  f32x4 acc[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[f][r] = 0.0f;
+
+  // lane = (column or channel c of the 16, k group kg of the 4)
+  const int c = lane & 15, kg = lane >> 4;
+  const int xfrag = kg * BN + ((wn * 16 + c) ^ ((kg & 1) << 4));
+  const int wfrag = (wm * 32 + c) * LDW + kg;
+  auto multiply = [&](int stage, int kk0) {
+    const float* xb_ = &xs[stage * XS + xfrag];
+    const float* wb_ = &ws[stage * WS + wfrag];
+#pragma unroll
+    for (int kk = kk0; kk < kk0 + BK / 2; kk += 4) {
+      const float a = xb_[kk * BN];
+      const float b0 = wb_[kk], b1 = wb_[16 * LDW + kk];
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[1], 0, 0, 0);
+    }
+  };
+
+  const int n_tiles = (K + BK - 1) / BK, n_whole = K / BK;
+  constexpr std::integral_constant<int, 0> ra{};
+  constexpr std::integral_constant<int, 1> rb{};
+  load_tile(0, ra);
+  if (n_tiles > 1) load_tile(1, rb);
+  store_tile(0, 0, ra);
+  if (n_tiles > 1) store_tile(1, 1, rb);
+  if (n_tiles > 2) load_tile(2, ra);
+  __syncthreads();
+  // at the top of step t: tiles t and t + 1 are in LDS, tile t + 2 is on its way to `hold`
+  int stage = 0;
+  auto step = [&](int t, auto hold, auto issue, auto guarded) {
+    constexpr bool G = decltype(guarded)::value;
+    if constexpr (!G) load_next_whole_tile(issue);
+    else if (t + 3 < n_tiles) load_tile(t + 3, issue);
+    multiply(stage, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // stage of tile t + 2 = stage of tile t - 1: last read before the previous barrier
+    if (!G || t + 2 < n_tiles) store_tile(stage == 0 ? 2 : stage - 1, t + 2, hold);
+    __builtin_amdgcn_sched_barrier(0);
+    multiply(stage, BK / 2);
+    stage = stage == 2 ? 0 : stage + 1;
+    __syncthreads();
+  };
+  // the body of the loop has no condition around its loads; the last steps, which have, run apart
+  int t = 0;
+  for (; t + 4 < n_whole; t += 2) {  // tiles t + 3 and t + 4 are whole
+    step(t, ra, rb, std::false_type{});
+    step(t + 1, rb, ra, std::false_type{});
+  }
+  for (; t < n_tiles; t += 2) {
+    step(t, ra, rb, std::true_type{});
+    if (t + 1 < n_tiles) step(t + 1, rb, ra, std::true_type{});
+  }
+
+  // epilogue: lane holds channel .. + c, positions 4 kg + 0..3 of the wave's 16 columns
+  const int col = n0 + wn * 16 + 4 * kg;
+  if (col >= n_total) return;
+  const unsigned b = fastdiv((unsigned)col, by_hw);
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int m = m0 + wm * 32 + f * 16 + c;
+    if (m >= M) continue;
+    const float bm = bias[m];
+    const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
+    float4 r;
+    r.x = activate<ACT>(acc[f][0] + bm);
+    r.y = activate<ACT>(acc[f][1] + bm);
+    r.z = activate<ACT>(acc[f][2] + bm);
+    r.w = activate<ACT>(acc[f][3] + bm);
+    if (residual) {  // the block's skip connection, added after the activation (K10's order)
+      const float4 q = *reinterpret_cast<const float4*>(residual + off);
+      r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+    }
+    *reinterpret_cast<float4*>(y + off) = r;
+  }
+}
+
 // The streaming configuration: short-K, few-channel projects (the FusedMBConv projects: K <= 256, M <= 64) whose whole
 // weight fits LDS.  There every element of x is used by one workgroup only, so its round trip through LDS in the
 // tiles above buys no reuse and costs a write, a barrier and a read per k-tile -- and with the input prologue the
@@ -524,7 +703,11 @@ __global__ __launch_bounds__(64 * kStWaves) void conv1x1_stream_kernel(
 //   stream(4 waves, each 32 t x 32 columns and all of M <= 96): the whole weight in LDS, x straight from global
 //                                    memory into the MFMA operand (conv1x1_stream_kernel above); a shape whose
 //                                    weight does not fit resolves to tall
-enum Conv1x1Config { kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2, kCfgDeepK = 3, kCfgStream = 4, kCfgCount = 5 };
+//   deep64(8 waves, each 32 x 16 of a 64 x 64 tile, k-tiles of 32 in a ring of three): deep-K's pipeline with half
+//                                    its W traffic (conv1x1_deep64_kernel above); takes every shape
+enum Conv1x1Config {
+  kCfgWide = 0, kCfgSquare = 1, kCfgTall = 2, kCfgDeepK = 3, kCfgStream = 4, kCfgDeep64 = 5, kCfgCount = 6
+};
 
 struct Conv1x1Plan { int cfg, waves_m, bm, bn; };
 
@@ -537,6 +720,8 @@ inline Conv1x1Plan plan_deepk(int M) {
   return {kCfgDeepK, w, 32 * w, kDkBN};
 }
 
+inline Conv1x1Plan plan_deep64() { return {kCfgDeep64, 2, kD6BM, kD6BN}; }  // waves_m: 2 x 4 waves
+
 // waves_m: the 32-row tiles every wave holds; bn: 128 columns per pass, two passes per workgroup where that still
 // leaves 1024 workgroups (one round of four per CU), so the weight is staged half as often
 inline Conv1x1Plan plan_stream(int M, int K, int HW, long long B) {
@@ -545,9 +730,26 @@ inline Conv1x1Plan plan_stream(int M, int K, int HW, long long B) {
   return {kCfgStream, (M + 31) / 32, (M + 31) / 32 * 32, 32 * kStWaves * t};
 }
 
+// The classes that measured faster on the 64 x 64 ring-staged tiles than on what they ran before, in every one of five
+// alternated rounds of graph replays at batch 64 (EfficientNetV2-S at 256 px): (M, K, HW).  A
+// list, not a rule: the same tiles lose where M is far from a multiple of 64 or K is short (MobileNetV3's M = 24, 80,
+// 200, 240, its expands behind K <= 112), and an unmeasured shape keeps the kernel it had.  (The four FusedMBConv
+// project classes measured faster too and are not here: see that section.)
+inline bool deep64_measured_faster(int M, int K, int HW) {
+  static const int classes[][3] = {
+      {256, 64, 1024}, {128, 256, 256}, {512, 128, 256}, {128, 512, 256},  // stage 4
+      {160, 768, 256}, {960, 160, 256}, {160, 960, 256},                   // stage 5
+      {256, 960, 64},  {1536, 256, 64}, {256, 1536, 64}, {1280, 256, 64},  // stage 6 and the head
+  };
+  for (const auto& c : classes)
+    if (c[0] == M && c[1] == K && c[2] == HW) return true;
+  return false;
+}
+
 inline Conv1x1Plan pick_config(int M, int K, int HW, long long B) {
   const long long n_total = B * HW;
   const long long n_tiles128 = (n_total + 127) / 128;
+  if (deep64_measured_faster(M, K, HW)) return plan_deep64();
   // the FusedMBConv projects on 64x64 maps (96 -> 48: 44.2 us against 52.9 on the tall tiles with the SiLU prologue,
   // 192 -> 48: 116.0 against 119.4, batch 64, every round); 192 -> 64 and 256 -> 64 on 32x32 maps measured 3 - 5 %
   // slower streamed and stay tall
@@ -574,6 +776,7 @@ inline int plan_for(int M, int K, int HW, long long B, int config, Conv1x1Plan* 
     case kCfgTall: *p = plan_tall(M); return MTR_OK;
     case kCfgDeepK: *p = plan_deepk(M); return MTR_OK;
     case kCfgStream: *p = plan_stream(M, K, HW, B); return MTR_OK;
+    case kCfgDeep64: *p = plan_deep64(); return MTR_OK;
     default: return MTR_E_PARAM;
   }
 }
@@ -668,6 +871,46 @@ static int launch_conv1x1_deepk(const float* x, const float* w, const float* bia
     default: return MTR_E_PARAM;
   }
 #undef MTR_DK_PRE
+}
+
+template <int PRE>
+static int launch_conv1x1_deep64_pre(const float* x, const float* w, const float* bias, const float* in_bias,
+                                     const float* gate, const float* residual, float* y, int act, int M, int K,
+                                     int HW, long long n_total, hipStream_t stream) {
+  const long long gx = (n_total + kD6BN - 1) / kD6BN, gy = (M + kD6BM - 1) / kD6BM;
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * kD6Waves);
+  const FastDiv by_hw = make_fastdiv((unsigned)HW);
+  MTR_CLEAR_STALE();
+#define MTR_D6_LAUNCH(ACT)                                                                                    \
+  hipLaunchKernelGGL((conv1x1_deep64_kernel<ACT, PRE>), grid, block, 0, stream, x, w, bias, in_bias, gate,    \
+                     residual, y, M, K, HW, (int)n_total, by_hw)
+  switch (act) {
+    case kActNone: MTR_D6_LAUNCH(kActNone); break;
+    case kActRelu: MTR_D6_LAUNCH(kActRelu); break;
+    case kActSilu: MTR_D6_LAUNCH(kActSilu); break;
+    case kActHardswish: MTR_D6_LAUNCH(kActHardswish); break;
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_D6_LAUNCH
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
+static int launch_conv1x1_deep64(const float* x, const float* w, const float* bias, const float* in_bias,
+                                 int in_act, const float* gate, const float* residual, float* y, int act, int M,
+                                 int K, int HW, long long n_total, hipStream_t stream) {
+#define MTR_D6_PRE(PRE) \
+  launch_conv1x1_deep64_pre<PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
+  switch (in_bias ? in_act : -1) {
+    case -1: return MTR_D6_PRE(-1);
+    case kActNone: return MTR_D6_PRE(kActNone);
+    case kActRelu: return MTR_D6_PRE(kActRelu);
+    case kActSilu: return MTR_D6_PRE(kActSilu);
+    case kActHardswish: return MTR_D6_PRE(kActHardswish);
+    default: return MTR_E_PARAM;
+  }
+#undef MTR_D6_PRE
 }
 
 template <int MT, int PRE>
@@ -779,6 +1022,7 @@ extern "C" int mtr_conv1x1_bias_act_pre(const void* x, int dtype, const float* w
         case 2: return mtr::launch_conv1x1_stream<2>(MTR_C1_ARGS_ST);
         default: return mtr::launch_conv1x1_stream<3>(MTR_C1_ARGS_ST);
       }
+    case mtr::kCfgDeep64: return mtr::launch_conv1x1_deep64(MTR_C1_ARGS);
     case mtr::kCfgDeepK:
       switch (p.waves_m) {
         case 4: return mtr::launch_conv1x1_deepk<4>(MTR_C1_ARGS);

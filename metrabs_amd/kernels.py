@@ -762,7 +762,7 @@ def conv1x1_supported(x, weight):
             and x.shape[0] * HW < 2 ** 31 and K * HW < 2 ** 31 and weight.shape[0] * HW < 2 ** 31)
 
 
-CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3, 'stream': 4}
+CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3, 'stream': 4, 'deep64': 5}
 
 
 def conv1x1_plan(M, K, HW, B, config='auto'):

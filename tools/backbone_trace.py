@@ -139,7 +139,7 @@ def _kind(kname):
         return 'K14h'
     if 'conv1x1_16_kernel' in k or 'conv1x1_16_deepk_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
         return 'K13h'
-    if 'conv1x1_kernel' in k:  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
+    if any(n in k for n in ('conv1x1_kernel', 'conv1x1_deepk_kernel', 'conv1x1_stream_kernel', 'conv1x1_deep64_kernel')):  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
         return 'K13'
     if 'bias_act' in k:
         return 'K10'
