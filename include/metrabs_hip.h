@@ -707,6 +707,32 @@ int mtr_stem_conv3x3s2(const void* x, int x_dtype, int layout, const void* weigh
  * work. */
 size_t mtr_stem_conv_lds_bytes(int dtype, long long B, int Cin, int Cout, int H, int W);
 
+/* K19 (outside the reference's hot path, like K10): a dense 3x3 convolution of f32 tensors -- stride 1, padding 1 on all
+ * sides, no dilation, groups 1 -- as Winograd F(2x2, 3x3) on the f32-input MFMA (v_mfma_f32_16x16x4_f32), with the K10
+ * epilogue folded in:
+ *   y[b, m, oy, ox] = act(bias[m] + sum_{ci, ky, kx} w[m, ci, ky, kx] * x[b, ci, oy + ky - 1, ox + kx - 1])
+ *                     (+ residual[b, m, oy, ox])
+ * evaluated per 2x2 output tile as Y = A^T [ sum_ci U[xi, m, ci] * (B^T d B)[xi, ci, tile] ] A with the standard
+ * matrices (entries 0, +-1, +-1/2).  x [B, Cin, H, W], y and residual [B, Cout, H, W]: f32, NCHW, contiguous, 16-byte
+ * aligned (else MTR_E_ALIGN).  weight_u is the weight ALREADY TRANSFORMED, U = G g G^T, computed in fp64 from the f32
+ * OIHW weight and rounded to f32 once, laid out [16][Cout][Cin] (xi = 4 i + j), contiguous, 16-byte aligned.  bias
+ * [Cout] f32; residual may be NULL and may be x itself; act as mtr_bias_act_nchw, applied in K10's order (bias,
+ * activation, then the residual), else MTR_E_PARAM.  The 16 products are f32 MFMA chains over ci = 0, 1, 2, ... in that
+ * one order; the input and output transforms use one fixed order of additions.  MTR_E_SHAPE (the caller keeps the
+ * library path) unless H is even, W % 4 == 0, Cin % 4 == 0, Cout >= 1, Cin H W and Cout H W below 2^31 and B H W / 4
+ * (the 2x2 tiles of the batch) below 2^31 - 64; maps of any such size are taken, partial workgroups included.  A NULL
+ * x, weight_u, bias or y is MTR_E_NULL; y overlapping x or residual is MTR_E_PARAM.  Every check is made on the host
+ * before anything is enqueued; B == 0 returns MTR_OK without a launch.  No atomics, no split-K, no workspace, nothing
+ * allocated; only enqueues on `stream`: the same inputs give the same bits for any batch index, on every call and
+ * graph replay (there is one tile configuration). */
+int mtr_conv3x3_winograd_bias_act(const void* x, const float* weight_u /*[16][Cout][Cin]*/, const float* bias,
+                                  const void* residual, int act, long long B, int Cin, int Cout, int H, int W,
+                                  void* y, mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_conv3x3_winograd_bias_act uses for this shape (one chunk of the transformed
+ * input and of U), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_conv3x3_winograd_lds_bytes(long long B, int Cin, int Cout, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

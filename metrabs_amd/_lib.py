@@ -180,6 +180,9 @@ SIGNATURES = {
     'mtr_stem_conv3x3s2': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                    ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_stem_conv_lds_bytes': (ctypes.c_size_t, [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_int]),
+    'mtr_conv3x3_winograd_bias_act': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                              c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_conv3x3_winograd_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

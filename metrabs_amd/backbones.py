@@ -161,8 +161,8 @@ class FusedMBConv(nn.Module):
     # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
     # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
     fused_pair = ()
-    # 'k16h' / 'k13_pre' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on every
-    # other block
+    # 'k16h' / 'k13_pre' / 'k19' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
+    # every other block
     last_path = None
     # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
     use_k16h = True
@@ -200,11 +200,16 @@ class FusedMBConv(nn.Module):
 
     def _forward_pre(self, x):
         """An armed f32 block.  'k13_pre': the 3x3 convolution alone, then ONE K13 launch that applies its epilogue,
-        the project and the skip.  'chain': what an unarmed block runs.  The tensor without its epilogue never leaves
-        this method."""
+        the project and the skip.  'k19' (fold_batchnorm(winograd3x3=True)): the 3x3 convolution WITH its epilogue on
+        K19, then the project and the skip on K13.  'chain': what an unarmed block runs.  The tensor without its
+        epilogue never leaves this method, and no tensor passes through two epilogues."""
         first, project = self.pre_pair
         c = first.conv
         residual = x if self.residual else None
+        if isinstance(first, WinogradConv3x3BiasAct) and first.k19_takes(x):
+            # K19 applies the 3x3 layer's own epilogue; the project is then a plain K13 call (no prologue) with the skip
+            self.last_path = 'k19'
+            return project(first(x), residual=residual)
         self.last_path = 'chain'
         if not (FusedMBConv.use_k13_pre and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
                 and c.weight.dtype == torch.float32 and not torch.is_autocast_enabled('cuda')
@@ -666,6 +671,72 @@ class StemConvBiasAct(ConvBiasAct):
         return super().forward(x, residual)
 
 
+class WinogradConv3x3BiasAct(ConvBiasAct):
+    """A folded dense 3x3, stride-1, padding-1 conv + BN (+ activation) of an f32 copy made with
+    fold_batchnorm(winograd3x3=True): the convolution as Winograd F(2x2, 3x3) on the f32 MFMA, "+ bias", the activation
+    and the block's skip as ONE HIP launch (K19, conv3x3_winograd.hip) instead of a MIOpen convolution followed by K10.
+    Same parameters and state_dict keys as the ConvBiasAct it replaces (the transformed weight is derived state, cached
+    per weight storage and version), which it also is for every input K19 does not take -- CPU, channels_last,
+    autocast, a gradient wanted, odd maps, the shapes listed as slower: those run exactly what ConvBiasAct runs."""
+
+    # class-wide switch (tests and A/B runs): the library path everywhere
+    use_k19 = True
+    # (Cin, Cout, H, W) of the input where K19 (for the expand of a FusedMBConv: K19 + the plain K13 project) was not
+    # ahead of the default copy's path in every round of tools/conv3x3_ab.py --dtype f32 (EfficientNetV2-S and ResNet-18
+    # batch 64 at 256 px, EfficientNetV2-L batch 32 at 384 px; DESIGN.md section 22, profiles/r18a_conv3x3_ab_winograd_*.jsonl)
+    k19_slower = frozenset({(512, 512, 8, 8)})
+
+    def __init__(self, conv, bias, act):
+        super().__init__(conv, bias, act)
+        self._wu = None
+        self.last_path = None  # 'k19' or 'library': what the last forward ran (tests, A/B runs)
+
+    @staticmethod
+    def applies_to(conv):
+        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
+                and conv.dilation == (1, 1) and conv.stride == (1, 1) and conv.padding == (1, 1)
+                and conv.padding_mode == 'zeros' and conv.in_channels % 4 == 0)
+
+    def weight_u(self):
+        """The conv's weight transformed for K19 ([16, Cout, Cin], kernels.pack_conv3x3_winograd_weight): made on the
+        first K19 forward and again whenever the weight has moved or been written since (not part of the state dict).
+        An inference tensor carries no version counter: a weight created under inference_mode and then written in
+        place keeps a stale U (as SqueezeExcite._fc2_wt); set self._wu = None after such a write."""
+        w = self.conv.weight
+        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
+        if self._wu is None or self._wu[0] != key:
+            from . import kernels
+            self._wu = (key, kernels.pack_conv3x3_winograd_weight(w))
+        return self._wu[1]
+
+    def k19_takes(self, x):
+        """Whether forward(x) runs on K19: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
+        the C entry accepts and that is not listed as slower."""
+        c = self.conv
+        if not (WinogradConv3x3BiasAct.use_k19 and not self.emit_mean and x.is_cuda and x.dim() == 4
+                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
+                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0):
+            return False
+        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (c.weight.requires_grad
+                                                                               or x.requires_grad)):
+            return False
+        B, K, H, W = x.shape
+        if K != c.in_channels or (K, c.out_channels, H, W) in WinogradConv3x3BiasAct.k19_slower:
+            return False
+        from . import _lib
+        return _lib.load().mtr_conv3x3_winograd_lds_bytes(B, K, c.out_channels, H, W) > 0
+
+    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
+        if not defer_epilogue and pre is None and self.k19_takes(x) and (
+                residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                     and residual.shape == (x.shape[0], self.conv.out_channels) + x.shape[2:]
+                                     and residual.data_ptr() % 16 == 0)):
+            from . import kernels
+            self.last_path = 'k19'
+            return kernels.conv3x3_winograd_bias_act(x, self.weight_u(), self.bias, self.act_name, residual=residual)
+        return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+
+
 class DepthwiseBiasAct(nn.Module):
     """A folded depthwise 3x3 (K11) or 5x5 (K15) conv + BN + activation as ONE HIP pass over the plane: the
     convolution, "+ bias", the activation and -- in front of a squeeze-excite block -- the
@@ -775,7 +846,7 @@ def _block_plus_skip(block, x):
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                   block_depthwise=False, deep_projects=False):
+                   block_depthwise=False, deep_projects=False, winograd3x3=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -817,7 +888,16 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     shapes of ConvBiasAct.k13h_slower, which run cast + x * gate + rocBLAS + K10 by default, included -- unless the
     shape is in ConvBiasAct.k13h_deep_slower; everything else takes today's branch.  The armed layers' results
     differ from the library chain's by rounding (another summation order), and are the bits of K13h's other
-    configurations.  A plain attribute on the layers: no module, buffer or state_dict key is added."""
+    configurations.  A plain attribute on the layers: no module, buffer or state_dict key is added.
+    winograd3x3=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype -- K14h serves the 16-bit copies; off by
+    default; independent of fuse_stem and block_depthwise) makes every dense 3x3, stride-1, padding-1, ungrouped
+    ConvBiasAct with Cin % 4 == 0 that emits no mean a WinogradConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L,
+    13 of ResNet-18, none of MobileNetV3.  Such a layer runs Winograd F(2x2, 3x3) on the f32 MFMA with "+ bias", the
+    activation and the block's skip in one launch (K19, .last_path 'k19') where that kernel takes the input and the
+    shape is not in WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed
+    FusedMBConv expand block runs K19 with its own epilogue and then the project as a plain K13 call (block
+    .last_path 'k19').  Results differ from the default copy's by rounding (both are Winograd evaluations with
+    different summation orders).  The state_dict keys are those of the copy without the option."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -834,6 +914,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: block_depthwise=True needs fused_epilogue=True')
     if deep_projects and dtype is None:
         raise ValueError('fold_batchnorm: deep_projects=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
+    if winograd3x3 and (dtype is not None or not fused_epilogue):
+        raise ValueError('fold_batchnorm: winograd3x3=True needs fused_epilogue=True and an f32 copy (no dtype=)')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -884,12 +966,18 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                 if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and \
                         isinstance(nxt[0], ConvBiasAct):
                     prev.gate_to = (nxt[0],)
+    if winograd3x3:  # dense 3x3 stride 1: Winograd on the f32 MFMA with the epilogue (K19)
+        for m in folded.modules():
+            if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct and not m[0].emit_mean \
+                    and WinogradConv3x3BiasAct.applies_to(m[0].conv):
+                m[0] = WinogradConv3x3BiasAct(m[0].conv, m[0].bias, m[0].act)
     if fused_epilogue and dtype is None:  # dense 3x3 -> project 1x1 of a FusedMBConv: the 3x3's epilogue inside K13
         for m in folded.modules():
             if isinstance(m, FusedMBConv) and list(m.block._modules) == ['0', '1']:
                 first, last = m.block._modules['0'], m.block._modules['1']
                 if isinstance(first, ConvBNAct) and isinstance(last, ConvBNAct) \
-                        and type(first[0]) is ConvBiasAct and type(last[0]) is ConvBiasAct \
+                        and type(first[0]) in (ConvBiasAct, WinogradConv3x3BiasAct) \
+                        and type(last[0]) is ConvBiasAct \
                         and all(isinstance(k, nn.Identity) for k in list(first)[1:] + list(last)[1:]) \
                         and first[0].conv.kernel_size == (3, 3) and first[0].conv.groups == 1 \
                         and not first[0].emit_mean and last[0].act is None and not last[0].emit_mean \

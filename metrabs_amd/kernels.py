@@ -1064,3 +1064,71 @@ def stem_conv_bias_act(x, weight, bias, act, preproc=False, out=None):
         dtype_code(weight.dtype), ACT_CODES[act], int(bool(preproc)), B, K, M, H, W, _ptr(out),
         current_stream_ptr(x.device)), 'mtr_stem_conv3x3s2')
     return out
+
+
+# K19: a dense 3x3 stride-1 convolution of f32 tensors as Winograd F(2x2, 3x3) on the f32 MFMA, with the K10 epilogue
+# (csrc/conv3x3_winograd.hip)
+
+_WINOGRAD_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def pack_conv3x3_winograd_weight(weight):
+    """The [Cout, Cin, 3, 3] f32 convolution weight as mtr_conv3x3_winograd_bias_act takes it: U = G g G^T per
+    (Cout, Cin) pair, computed in fp64 and rounded to f32 once, laid out [16, Cout, Cin] (xi = 4 i + j), contiguous.
+    Plain torch; done once per weight."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f'pack_conv3x3_winograd_weight: expected [Cout, Cin, 3, 3], got {tuple(weight.shape)}')
+    if weight.dtype != torch.float32:
+        raise ValueError(f'pack_conv3x3_winograd_weight: expected an f32 weight, got {weight.dtype}')
+    g = weight.detach().double()
+    G = torch.tensor(_WINOGRAD_G, dtype=torch.float64, device=g.device)
+    u = torch.einsum('ik,mckl,jl->ijmc', G, g, G)   # [4, 4, Cout, Cin]
+    return u.reshape(16, weight.shape[0], weight.shape[1]).float().contiguous()
+
+
+def conv3x3_winograd_supported(x, w_u):
+    """Whether mtr_conv3x3_winograd_bias_act takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
+    aligned, w_u [16, Cout, Cin] f32 contiguous (pack_conv3x3_winograd_weight), H even, W and Cin multiples of 4 (its
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
+    if x.dim() != 4 or w_u.dim() != 3 or x.dtype != torch.float32 or w_u.dtype != torch.float32 \
+            or not x.is_cuda or not w_u.is_cuda or not x.is_contiguous() or not w_u.is_contiguous() \
+            or x.data_ptr() % 16 or w_u.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if w_u.shape[0] != 16 or w_u.shape[2] != K:
+        return False
+    return _lib.load().mtr_conv3x3_winograd_lds_bytes(B, K, w_u.shape[1], H, W) > 0
+
+
+def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
+    """y = act(conv3x3(x, w, stride 1, padding 1) + bias) (+ residual) in one launch on the current stream, for f32:
+    x [B, Cin, H, W] NCHW-contiguous, w_u [16, Cout, Cin] (pack_conv3x3_winograd_weight), bias [Cout] f32, residual
+    [B, Cout, H, W] f32 or None (it may be x).  Winograd F(2x2, 3x3) with f32 MFMA chains in a fixed order: the same
+    bits on every call and graph replay."""
+    require_cuda(x, w_u, bias, residual)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('conv3x3_winograd_bias_act: x must be [B, Cin, H, W], NCHW-contiguous')
+    if x.dtype != torch.float32 or w_u.dtype != torch.float32:
+        raise ValueError(f'conv3x3_winograd_bias_act: x and the weight must be f32, got {x.dtype} and {w_u.dtype}')
+    B, K, H, W = x.shape
+    if w_u.dim() != 3 or w_u.shape[0] != 16 or w_u.shape[2] != K or not w_u.is_contiguous():
+        raise ValueError(f'conv3x3_winograd_bias_act: the weight must be transformed [16, Cout, {K}] and contiguous, '
+                         f'got {tuple(w_u.shape)}')
+    M = w_u.shape[1]
+    if bias.numel() != M:
+        raise ValueError(f'conv3x3_winograd_bias_act: bias has {bias.numel()} elements, expected {M}')
+    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
+                                 or not residual.is_contiguous()):
+        raise ValueError('conv3x3_winograd_bias_act: residual must be [B, Cout, H, W] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('conv3x3_winograd_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
+    for t, name in ((x, 'x'), (residual, 'residual')):
+        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
+                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError(f'conv3x3_winograd_bias_act: out must not overlap {name}')
+    check(_lib.load().mtr_conv3x3_winograd_bias_act(
+        _ptr(x), _ptr(w_u), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3_winograd_bias_act')
+    return out

@@ -27,6 +27,9 @@ kernel).  The arms return the same poses bit for bit.  The rows carry ab='k18'.
 --ab deepk: both arms are the 16-bit copy of the same network (--config 1 or 4), A folded as by default, B with
 deep_projects=True (the deep project convolutions on K13h's deep-K configuration instead of cast + x * gate + rocBLAS +
 K10).  The arms differ by rounding; the rows carry ab='deepk' and the paths of the armed layers.
+--ab k19: both arms are the f32 copy of the same network (--dtype f32; --config 1), A folded as by default, B with
+winograd3x3=True (the dense 3x3 stride-1 layers on K19 where WinogradConv3x3BiasAct.k19_slower does not list them).  The
+arms differ by rounding; the rows carry ab='k19' and the paths of the armed layers.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -46,14 +49,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19'], default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
-                         "k18: without vs with block_depthwise; deepk: without vs with deep_projects")
+                         "k18: without vs with block_depthwise; deepk: without vs with deep_projects; "
+                         "k19 (--dtype f32): the f32 copy folded without vs with winograd3x3")
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18'):
-        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17 or --ab k18')
+    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19'):
+        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18 or --ab k19')
+    if args.ab == 'k19' and args.dtype != 'f32':
+        ap.error('--ab k19 goes with --dtype f32')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -95,6 +101,14 @@ def main():
             if dt is None:
                 e.crop_model.autocast_dtype = None               # f32 copies, run in f32
         assert any(isinstance(m, DepthwiseBiasAct) and m.block_depthwise for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k19':                                         # both arms the f32 copy, B with K19 armed
+        from metrabs_amd.backbones import WinogradConv3x3BiasAct
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True)
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, winograd3x3=True)
+        for e in (est_a, est_b):
+            e.crop_dtype = e.crop_model.input_dtype
+            e.crop_model.autocast_dtype = None                   # f32 copies, run in f32
+        assert any(isinstance(m, WinogradConv3x3BiasAct) for m in est_b.crop_model.backbone.modules())
     if args.ab == 'deepk':                                       # both arms the 16-bit copy, B with its deep projects armed
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -185,6 +199,13 @@ def main():
         row = dict(kind='paths', ab='k18', equal_poses=bool(torch.equal(p_a, p_b)),
                    a={k: paths[0].count(k) for k in sorted(set(paths[0]))},
                    b={k: paths[1].count(k) for k in sorted(set(paths[1]))})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k19':
+        from metrabs_amd.backbones import WinogradConv3x3BiasAct
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules() if isinstance(m, WinogradConv3x3BiasAct)]
+        row = dict(kind='paths', ab='k19', mpjpe_armed_vs_default_mm=round(float((p_b - p_a).norm(dim=-1).mean()), 5),
+                   b={k: paths.count(k) for k in sorted(set(paths))})
         print(json.dumps(row), flush=True)
         rows.append(row)
     if args.ab == 'deepk':

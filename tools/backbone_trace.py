@@ -65,6 +65,7 @@ def record(args):
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
                          dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
                          fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise,
+                         winograd3x3=args.winograd3x3,
                          deep_projects=args.deep_projects)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
@@ -135,6 +136,8 @@ def _kind(kname):
         return 'K17'
     if 'fused_mbconv16_kernel' in k:  # K16h: a whole FusedMBConv block (3x3 expand + 1x1 project) of the 16-bit copy
         return 'K16h'
+    if 'conv3x3_winograd_kernel' in k:  # K19 (before the generic 'conv' match): the f32 dense 3x3 Winograd conv + epilogue
+        return 'K19'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
         return 'K14h'
     if 'conv1x1_16_kernel' in k or 'conv1x1_16_deepk_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
@@ -206,19 +209,19 @@ def _fused_table(per_kernel, pat):
             continue
         b = rows.setdefault(key, defaultdict(float))
         if layer == 0:
-            col = 'K14h' if kind == 'K14h' else 'K10' if kind == 'K10' else 'dense conv'
+            col = kind if kind in ('K14h', 'K19', 'K10') else 'dense conv'
             if col == 'dense conv' and key != 'stem':
                 served[f'{kind}: {kname[:60]}'] += us
         else:
             col = 'project'   # (K13h, or the library GEMM + K10)
         b[col] += us
-    cols = ['dense conv', 'K14h', 'K10', 'project', 'K16h']
+    cols = ['dense conv', 'K14h', 'K19', 'K10', 'project', 'K16h']
     lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project '
                  '(or K16h: all of them in one launch)', '',
              '| stage.block | ' + ' | '.join(cols) + ' | **3x3 + K10** |', '|---|' + '---|' * (len(cols) + 1)]
     sums = defaultdict(float)
     for key, b in rows.items():
-        dense = b['dense conv'] + b['K14h'] + b['K10']
+        dense = b['dense conv'] + b['K14h'] + b['K19'] + b['K10']
         for c in cols:
             sums[c] += b[c]
         sums['dense'] += dense
@@ -228,7 +231,7 @@ def _fused_table(per_kernel, pat):
     lines.append('| **sum** | ' + ' | '.join(f'{sums[c]:.1f}' for c in cols) + f' | **{sums["dense"]:.1f}** |')
     lines += ['', f'Dense 3x3 layers of stages 1 - 3 with their epilogue (without the stem): '
                   f'**{sums["dense_blocks"]:.1f} us**.']
-    slice23 = sum(b['dense conv'] + b['K14h'] + b['K10'] + b['project'] + b['K16h']
+    slice23 = sum(b['dense conv'] + b['K14h'] + b['K19'] + b['K10'] + b['project'] + b['K16h']
                   for key, b in rows.items() if key.split('.')[0] in ('2', '3'))
     lines += ['', f'Dense 3x3 + project of stages 2 - 3 (K16h included): **{slice23:.1f} us**.']
     if served:
@@ -363,6 +366,8 @@ def main():
     r.add_argument('--block-depthwise', action='store_true',
                    help='fold with block_depthwise=True: the stride-1 depthwise 3x3 layers on K18 where K11 would take '
                         'its generic kernel')
+    r.add_argument('--winograd3x3', action='store_true',
+                   help='fold with winograd3x3=True (f32 only): the dense 3x3 stride-1 layers on K19')
     r.add_argument('--deep-projects', action='store_true',
                    help='fold with deep_projects=True (a -copy precision only): the deep project convolutions on '
                         "K13h's deep-K configuration")

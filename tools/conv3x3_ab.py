@@ -11,6 +11,16 @@ forward of the folded copy; each arm is captured as a HIP graph of --iters calls
 device events, the two arms alternated in --rounds rounds, the median per-call time reported with its share of
 the 16-bit MFMA peak (2.5 PF) and of the byte floor (one 16-bit read of x, w and the skip, one write of y, at the
 measured 6.29 TB/s copy rate of an MI355X).  Shapes the C entry declines are reported with k14h_us null.
+
+    python tools/conv3x3_ab.py --dtype f32 --out OUT.jsonl      # K19 against what the f32 copy runs by default
+
+--dtype f32: per shape class of the f32 copy folded with winograd3x3=True, K19 (kernels.conv3x3_winograd_bias_act)
+against what the class runs in the default copy, by the same method.  A layer that stands alone (EfficientNetV2 stage
+1, ResNet-18): the MIOpen convolution, pinned to the deterministic solvers as the f32 bench runs it, + K10.  The expand
+of a FusedMBConv block (stages 2 - 3) is timed as the PAIR, because the prologue moves cost between the two kernels:
+MIOpen convolution + K13 with the prologue against K19 + the plain K13 call.  Every record carries the per-round times
+of both arms, the share of the 155 TF f32 matrix peak counted in Winograd-domain FLOP (16 products per 2x2 tile and
+channel pair; the pair's project not counted) and the share of the byte floor of the 3x3 layer.
 """
 import argparse
 import json
@@ -18,7 +28,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAK16_TF, HBM_TBS = 2500.0, 6.29
+PEAK16_TF, PEAK32_TF, HBM_TBS = 2500.0, 155.0, 6.29
 
 
 def shape_classes(res, backbone, dtype):
@@ -41,17 +51,164 @@ def shape_classes(res, backbone, dtype):
     return out
 
 
+def shape_classes_f32(res, backbone):
+    """(Cin, Cout, H, W, act, skip, project Cout or None) -> module names, from a hooked forward of the armed copy."""
+    import torch
+    from metrabs_amd import backbones
+    W3 = backbones.WinogradConv3x3BiasAct
+    net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True,
+                                   winograd3x3=True).cuda()
+    out, paired = {}, set()
+    for name, m in net.named_modules():
+        if isinstance(m, backbones.FusedMBConv) and m.pre_pair and isinstance(m.pre_pair[0], W3):
+            paired.add(m.pre_pair[0])
+
+            def hook(mod, args, name=name):
+                x, (first, project) = args[0], mod.pre_pair
+                key = (x.shape[1], first.conv.out_channels, x.shape[2], x.shape[3], first.act_name, mod.residual,
+                       project.conv.out_channels)
+                out.setdefault(key, []).append(name)
+            m.register_forward_pre_hook(hook)
+    for name, m in net.named_modules():
+        if isinstance(m, W3) and m not in paired:
+            def hook(mod, args, kwargs, name=name):
+                x = args[0]
+                key = (x.shape[1], mod.conv.out_channels, x.shape[2], x.shape[3], mod.act_name,
+                       kwargs.get('residual') is not None, None)
+                out.setdefault(key, []).append(name)
+            m.register_forward_pre_hook(hook, with_kwargs=True)
+    W3.use_k19 = False
+    try:
+        with torch.inference_mode():
+            net(torch.rand(1, 3, res, res, device='cuda'))
+    finally:
+        W3.use_k19 = True
+    return out
+
+
+def main_f32(args):
+    import torch
+    import torch.nn.functional as F
+    from metrabs_amd import kernels
+    classes = shape_classes_f32(args.res, args.backbone)
+    rows = []
+    g = torch.Generator(device='cuda').manual_seed(0)
+    B = args.batch
+    med = lambda v: sorted(v)[len(v) // 2]
+    for (K, M, H, W, act, skip, P), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+        x = torch.randn(B, K, H, W, device='cuda', generator=g)
+        w = torch.randn(M, K, 3, 3, device='cuda', generator=g) / (9 * K) ** 0.5
+        wu = kernels.pack_conv3x3_winograd_weight(w)
+        b = torch.randn(M, device='cuda', generator=g)
+        y = torch.empty(B, M, H, W, device='cuda')
+        supported = kernels.conv3x3_winograd_supported(x, wu)
+        if P is None:
+            r = torch.randn(B, M, H, W, device='cuda', generator=g) if skip else None
+
+            def old():
+                yy = F.conv2d(x, w, None, 1, 1)
+                kernels.bias_act_(yy, b, act, r)
+                return yy
+
+            def new():
+                return kernels.conv3x3_winograd_bias_act(x, wu, b, act, residual=r, out=y)
+        else:
+            w1 = torch.randn(P, M, 1, 1, device='cuda', generator=g) / M ** 0.5
+            b1 = torch.randn(P, device='cuda', generator=g)
+            r = torch.randn(B, P, H, W, device='cuda', generator=g) if skip else None
+
+            def old():
+                return kernels.conv1x1_bias_act(F.conv2d(x, w, None, 1, 1), w1, b1, None, residual=r, in_bias=b,
+                                                in_act=act)
+
+            def new():
+                kernels.conv3x3_winograd_bias_act(x, wu, b, act, out=y)
+                return kernels.conv1x1_bias_act(y, w1, b1, None, residual=r)
+
+        def captured(fn):
+            st = torch.cuda.Stream()
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                fn()
+                st.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=st, capture_error_mode='thread_local'):
+                    for _ in range(args.iters):
+                        fn()
+            torch.cuda.current_stream().wait_stream(st)
+            torch.cuda.synchronize()
+            return graph
+
+        def timed(graph):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            graph.replay()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
+
+        with torch.inference_mode(), torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):
+            a = old()
+            diff = None
+            if supported:
+                c = new()
+                torch.cuda.synchronize()
+                diff = float((a - c).abs().max() / a.abs().max().clamp_min(1e-30))
+            for _ in range(3):
+                old()
+                if supported:
+                    new()
+            arm_old = captured(old)
+            arm_new = captured(new) if supported else None
+            for _ in range(2):
+                timed(arm_old)
+                if supported:
+                    timed(arm_new)
+            t_old, t_new = [], []
+            for _ in range(args.rounds):
+                t_old.append(timed(arm_old))
+                if supported:
+                    t_new.append(timed(arm_new))
+            del arm_old, arm_new
+        wino_flop = 2.0 * B * (H // 2) * (W // 2) * 16 * K * M
+        byts = 4 * (B * H * W * (K + M * (2 if (skip and P is None) else 1)) + 16 * M * K)
+        byte_floor = byts / (HBM_TBS * 1e12) * 1e6
+        row = dict(cin=K, cout=M, hw=f'{H}x{W}', act=act, skip=skip, project_cout=P,
+                   timed='pair with the K13 project' if P is not None else 'layer', layers=len(names), first=names[0],
+                   dtype='f32', batch=B, res=args.res, backbone=args.backbone,
+                   direct_gflop=round(2.0 * B * H * W * 9 * K * M / 1e9, 2), winograd_gflop=round(wino_flop / 1e9, 2),
+                   mbytes=round(byts / 1e6, 1), old_us=round(med(t_old), 2), old_us_rounds=[round(t, 2) for t in t_old],
+                   k19_us=None)
+        if supported:
+            t = med(t_new)
+            row.update(k19_us=round(t, 2), k19_us_rounds=[round(v, 2) for v in t_new],
+                       speedup=round(med(t_old) / t, 3), k19_ahead_in_every_round=max(t_new) < min(t_old),
+                       rel_diff=diff, byte_floor_us=round(byte_floor, 2))
+            if P is None:   # (of a pair only the sum is timed: no share for the 3x3 layer alone)
+                row.update(k19_winograd_tflops=round(wino_flop / t / 1e6, 1),
+                           k19_share_of_f32_peak=round(wino_flop / t / 1e6 / PEAK32_TF, 3),
+                           share_of_byte_floor=round(byte_floor / t, 3))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        for r in rows:
+            f.write(json.dumps(r) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--res', type=int, default=256)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--dtype', choices=['f16', 'bf16'], default='f16')
+    ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--backbone', default='effnetv2-s')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
+    if args.dtype == 'f32':
+        return main_f32(args)
     import torch
     import torch.nn.functional as F
     from metrabs_amd import kernels
