@@ -733,6 +733,34 @@ int mtr_conv3x3_winograd_bias_act(const void* x, const float* weight_u /*[16][Co
  * input and of U), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_conv3x3_winograd_lds_bytes(long long B, int Cin, int Cout, int H, int W);
 
+/* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
+ * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
+ *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32
+ *   y[b, m, p] = act(bias[m] + sum_k w[m, k] * v[b, k, p]) (+ residual[b, m, p])
+ * An f32 value is exactly the sum of three bf16 values, a0 = bf16_rn(a), a1 = bf16_rn(a - a0), a2 = bf16_rn(a - a0 -
+ * a1).  w_split is the weight ALREADY SPLIT that way: [3][M][Kp] bf16, Kp = K rounded up to 32, the tail zero,
+ * contiguous, 16-byte aligned.  v is split inside the kernel.  Per 32-k block and output the six products (w2, v0),
+ * (w0, v2), (w1, v1), (w1, v0), (w0, v1), (w0, v0) are accumulated in that order into one f32 accumulator, the blocks
+ * in k order: everything above 2^-23 |w v| is kept, and the result passes the fp64 bound K13 is tested with, but it is
+ * NOT the bits of mtr_conv1x1_bias_act_pre.  x [B, K, HW], y and residual [B, M, HW]: f32, NCHW, contiguous, 16-byte
+ * aligned (else MTR_E_ALIGN); bias [M], in_bias [K] (4-byte aligned) or NULL (in_act must then be 0, else
+ * MTR_E_PARAM), gate [B, K] or NULL, residual or NULL; act / in_act as mtr_bias_act_nchw, the residual added after
+ * the activation.  HW and K multiples of 4, B >= 0, M >= 1, B HW, K HW and M HW below 2^31 (else MTR_E_SHAPE); a NULL
+ * x, w_split, bias or y is MTR_E_NULL; y overlapping x or the residual, or the residual being x, is MTR_E_PARAM.
+ * Checked in that order -- NULL, shape, parameters, alignment, overlap -- on the host before anything is enqueued;
+ * B == 0 returns MTR_OK without a launch.  Non-finite inputs: a - bf16(a) of an infinity is NaN, so a column of x
+ * that holds an infinity (or a finite value of 2^127 (2 - 2^-8) or more, which rounds to one) gives NaN where
+ * mtr_conv1x1_bias_act_pre gives an infinity; finite inputs below 2^127 behave as described.  No atomics, no
+ * split-K, no workspace, nothing allocated; only enqueues on `stream`: the same inputs give the same bits on every
+ * call and graph replay (the tile is a function of the shape and does not change the bits). */
+int mtr_conv1x1_bias_act_split(const void* x, const void* w_split /*[3][M][Kp] bf16*/, const float* bias,
+                               const float* in_bias /*[K] or NULL*/, int in_act,
+                               const float* gate /*[B*K] or NULL*/, const void* residual, int act, long long B,
+                               int M, int K, int HW, void* y, mtr_stream_t stream);
+
+/* Host only: MTR_OK where mtr_conv1x1_bias_act_split takes the shape, else what it answers (MTR_E_SHAPE). */
+int mtr_conv1x1_split_supported(long long B, int M, int K, int HW);
+
 #ifdef __cplusplus
 }
 #endif

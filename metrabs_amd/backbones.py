@@ -161,7 +161,7 @@ class FusedMBConv(nn.Module):
     # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
     # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
     fused_pair = ()
-    # 'k16h' / 'k13_pre' / 'k19' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
+    # 'k16h' / 'k13_pre' / 'k20_pre' / 'k19' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
     # every other block
     last_path = None
     # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
@@ -218,8 +218,8 @@ class FusedMBConv(nn.Module):
                 not in FusedMBConv.k13_pre_slower):
             return _block_plus_skip(self.block, x) if self.residual else self.block(x)
         y = first(x, defer_epilogue=True)
-        if project.k13_accepts(y, residual):
-            self.last_path = 'k13_pre'
+        if project.k13_accepts(y, residual):  # (fold_batchnorm(split_gemm=True): the same launch on K20 where it takes y)
+            self.last_path = 'k20_pre' if project.k20_takes(y) else 'k13_pre'
             return project(y, residual=residual, pre=first)
         return project(_finish_bias_act(first, y, None), residual=residual)
 
@@ -398,8 +398,8 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        # 'k13', 'k13_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate' or 'library': what the last forward ran
-        # (tests, A/B runs)
+        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate' or 'library': what the
+        # last forward ran (tests, A/B runs)
         self.last_path = None
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
@@ -428,6 +428,45 @@ class ConvBiasAct(nn.Module):
         """k13_takes(x), and a skip connection K13's epilogue can add: x's dtype, contiguous, 16-byte aligned."""
         return self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
                                                            and residual.data_ptr() % 16 == 0))
+
+    # fold_batchnorm(split_gemm=True) sets this on the 1x1, stride-1, unpadded, ungrouped layers of an f32 copy that emit
+    # no mean: they run K20 (conv1x1_split.hip, the product on the bf16 matrix cores from split operands) wherever K13
+    # would take the input
+    split_gemm = False
+    # class-wide switch (tests and A/B runs): the armed layers on K13 again
+    use_k20 = True
+    # (Cin, Cout, H * W) where K20 was not ahead of K13 in every round of tools/conv1x1_ab.py --ab k20 (EfficientNetV2-S
+    # batch 64 at 256 px, MobileNetV3 batch 320 at 256 px, EfficientNetV2-L batch 32 at 384 px; DESIGN.md section 23,
+    # profiles/r19a_conv1x1_ab_k20_*.jsonl): these keep K13.  All but three are expands (few input channels, many
+    # output channels)
+    k20_slower = frozenset({(64, 256, 1024), (128, 768, 256), (256, 1536, 64), (256, 1280, 64),
+                            (80, 480, 256), (112, 672, 256), (16, 16, 16384), (64, 24, 4096), (72, 24, 4096),
+                            (40, 240, 1024), (80, 200, 256), (96, 384, 2304)})
+    _ws = None
+
+    def weight_split(self):
+        """The conv's weight split for K20 ([3, Cout, Kp] bf16, kernels.pack_conv1x1_split_weight): made on the first
+        K20 forward and again whenever the weight has moved or been written since (not part of the state dict).  An
+        inference tensor carries no version counter (as WinogradConv3x3BiasAct.weight_u): set self._ws = None after
+        writing such a weight in place."""
+        w = self.conv.weight
+        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
+        if self._ws is None or self._ws[0] != key:
+            from . import kernels
+            self._ws = (key, kernels.pack_conv1x1_split_weight(w))
+        return self._ws[1]
+
+    def k20_takes(self, x):
+        """Whether forward(x) runs on K20: an armed layer, the switch on, everything k13_takes(x) asks for, a shape the
+        C entry accepts and that is not listed as slower, no gradient wanted for x either."""
+        if not (self.split_gemm and ConvBiasAct.use_k20 and self.k13_takes(x)):
+            return False
+        c = self.conv
+        if (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k20_slower:
+            return False
+        from . import _lib
+        return _lib.load().mtr_conv1x1_split_supported(x.shape[0], c.out_channels, c.in_channels,
+                                                       x.shape[2] * x.shape[3]) == 0
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions of a 16-bit copy on K13h instead of
     # rocBLAS + K10 (+ x * gate)
@@ -500,7 +539,12 @@ class ConvBiasAct(nn.Module):
             return self.conv(x)
         if pre is not None:  # (the block asked k13_accepts(x, residual) for this very tensor)
             from . import kernels
-            self._gate, self.last_path = None, 'k13'
+            self._gate = None
+            if self.k20_takes(x):
+                self.last_path = 'k20'
+                return kernels.conv1x1_bias_act_split(x, self.weight_split(), self.bias, self.act_name,
+                                                      residual=residual, in_bias=pre.bias, in_act=pre.act_name)
+            self.last_path = 'k13'
             return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, residual=residual,
                                             in_bias=pre.bias, in_act=pre.act_name)
         held, self._gate = self._gate, None
@@ -522,6 +566,10 @@ class ConvBiasAct(nn.Module):
                                               residual=residual)
         if self.k13_accepts(x, residual):
             from . import kernels
+            if self.k20_takes(x):
+                self.last_path = 'k20' if gate is None else 'k20_gate'
+                return kernels.conv1x1_bias_act_split(x, self.weight_split(), self.bias, self.act_name, gate=gate,
+                                                      residual=residual)
             self.last_path = 'k13' if gate is None else 'k13_gate'
             return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, gate=gate,
                                             residual=residual)
@@ -846,7 +894,7 @@ def _block_plus_skip(block, x):
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                   block_depthwise=False, deep_projects=False, winograd3x3=False):
+                   block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -897,7 +945,15 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     shape is not in WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed
     FusedMBConv expand block runs K19 with its own epilogue and then the project as a plain K13 call (block
     .last_path 'k19').  Results differ from the default copy's by rounding (both are Winograd evaluations with
-    different summation orders).  The state_dict keys are those of the copy without the option."""
+    different summation orders).  The state_dict keys are those of the copy without the option.
+    split_gemm=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype; off by default; independent of every other
+    option) arms every ConvBiasAct that is 1x1, stride 1, unpadded, ungrouped and emits no mean -- the expand, project
+    and head-side 1x1 layers: such a layer runs K20 (.last_path 'k20' / 'k20_gate'; an armed FusedMBConv block reports
+    'k20_pre') wherever K13 would take the input, unless the shape is in ConvBiasAct.k20_slower: the f32 product on the
+    bf16 matrix cores, from operands split into three bf16 pieces each and the six largest of the nine cross products,
+    with K13's prologue, gate, epilogue and skip.  f32-grade (it passes K13's fp64 bound) but not K13's bits.
+    Everything K20 refuses runs exactly today's branch.  A plain attribute on the layers: no module, buffer or
+    state_dict key is added; the split weight is derived state, cached per weight storage and version."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
@@ -916,6 +972,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: deep_projects=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
     if winograd3x3 and (dtype is not None or not fused_epilogue):
         raise ValueError('fold_batchnorm: winograd3x3=True needs fused_epilogue=True and an f32 copy (no dtype=)')
+    if split_gemm and (dtype is not None or not fused_epilogue):
+        raise ValueError('fold_batchnorm: split_gemm=True needs fused_epilogue=True and an f32 copy (no dtype=)')
     folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
@@ -1016,6 +1074,12 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
             if c is not None and m.act is None and c.kernel_size == (1, 1) and c.stride == (1, 1) \
                     and c.padding == (0, 0) and c.groups == 1 and c.in_channels >= 768 and c.out_channels > 160:
                 m.deep_projects = True
+    if split_gemm:  # 1x1 stride 1: the f32 product on the bf16 matrix cores from split operands (K20)
+        for m in folded.modules():
+            c = m.conv if isinstance(m, ConvBiasAct) else None
+            if c is not None and not m.emit_mean and c.kernel_size == (1, 1) and c.stride == (1, 1) \
+                    and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1:
+                m.split_gemm = True
     if fuse_stem:  # Preproc -> stem 3x3 stride 2: one launch (K17)
         stem_blk = next((m for m in folded.modules() if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct
                          and not m[0].emit_mean and StemConvBiasAct.applies_to(m[0].conv)), None)

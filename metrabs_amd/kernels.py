@@ -1132,3 +1132,84 @@ def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
         _ptr(x), _ptr(w_u), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
         ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3_winograd_bias_act')
     return out
+
+
+# K20: a 1x1 stride-1 convolution of f32 tensors on the bf16 matrix cores, from operands split into three bf16 pieces
+# (csrc/conv1x1_split.hip)
+
+def pack_conv1x1_split_weight(weight):
+    """The [M, K] (or [M, K, 1, 1]) f32 weight as mtr_conv1x1_bias_act_split takes it: [3, M, Kp] bf16, Kp = K rounded
+    up to 32 with a zero tail, w0 = bf16_rn(w), w1 = bf16_rn(w - w0), w2 = bf16_rn(w - w0 - w1).  The subtractions are
+    exact in f32 and w0 + w1 + w2 == w bit for bit (asserted) for finite weights whose third piece does not underflow.
+    Plain torch; done once per weight."""
+    if weight.dim() not in (2, 4) or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
+        raise ValueError(f'pack_conv1x1_split_weight: expected [M, K] or [M, K, 1, 1], got {tuple(weight.shape)}')
+    if weight.dtype != torch.float32:
+        raise ValueError(f'pack_conv1x1_split_weight: expected an f32 weight, got {weight.dtype}')
+    w = weight.detach().reshape(weight.shape[0], -1)
+    M, K = w.shape
+    w0 = w.to(torch.bfloat16)
+    r1 = w - w0.float()
+    w1 = r1.to(torch.bfloat16)
+    r2 = r1 - w1.float()
+    w2 = r2.to(torch.bfloat16)
+    if not torch.equal(w0.float() + w1.float() + w2.float(), w):
+        raise AssertionError('pack_conv1x1_split_weight: the three bf16 pieces do not sum back to the weight '
+                             '(non-finite or subnormal-range values)')
+    Kp = (K + 31) // 32 * 32
+    out = torch.zeros(3, M, Kp, dtype=torch.bfloat16, device=w.device)
+    out[0, :, :K], out[1, :, :K], out[2, :, :K] = w0, w1, w2
+    return out
+
+
+def conv1x1_split_supported(x, w_split):
+    """Whether mtr_conv1x1_bias_act_split takes this input: CUDA f32 x [B, K, H, W], NCHW-contiguous and 16-byte
+    aligned, w_split [3, M, Kp] bf16 contiguous (pack_conv1x1_split_weight), H*W and K multiples of 4 (its
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
+    if x.dim() != 4 or w_split.dim() != 3 or x.dtype != torch.float32 or w_split.dtype != torch.bfloat16 \
+            or not x.is_cuda or not w_split.is_cuda or not x.is_contiguous() or not w_split.is_contiguous() \
+            or x.data_ptr() % 16 or w_split.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if w_split.shape[0] != 3 or w_split.shape[2] != (K + 31) // 32 * 32:
+        return False
+    return _lib.load().mtr_conv1x1_split_supported(B, w_split.shape[1], K, H * W) == 0
+
+
+def conv1x1_bias_act_split(x, w_split, bias, act, gate=None, residual=None, in_bias=None, in_act=None, out=None):
+    """conv1x1_bias_act for f32 tensors on the bf16 matrix cores (K20): y = act(conv1x1(v, w) + bias) (+ residual),
+    v = in_act(x + in_bias) (x itself without in_bias) times gate[:, :, None, None], in one launch on the current
+    stream.  x [B, K, H, W] f32 NCHW-contiguous, w_split [3, M, Kp] bf16 (pack_conv1x1_split_weight), bias [M],
+    gate [B, K] f32 or None, residual [B, M, H, W] or None, in_bias [K] f32 or None.  The f32 product is summed from
+    six bf16 products of the split operands in a fixed order: f32-grade against fp64 (K13's bound), the same bits on
+    every call and graph replay, but not the bits of conv1x1_bias_act."""
+    require_cuda(x, w_split, bias, gate, residual, in_bias)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('conv1x1_bias_act_split: x must be [B, K, H, W] f32, NCHW-contiguous')
+    B, K, H, W = x.shape
+    if w_split.dim() != 3 or w_split.shape[0] != 3 or w_split.dtype != torch.bfloat16 \
+            or w_split.shape[2] != (K + 31) // 32 * 32 or not w_split.is_contiguous():
+        raise ValueError(f'conv1x1_bias_act_split: the weight must be split [3, M, {(K + 31) // 32 * 32}] bf16 and '
+                         f'contiguous for {K} input channels, got {tuple(w_split.shape)} {w_split.dtype}')
+    M = w_split.shape[1]
+    if bias.numel() != M:
+        raise ValueError(f'conv1x1_bias_act_split: bias has {bias.numel()} elements, expected {M}')
+    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != B * K):
+        raise ValueError('conv1x1_bias_act_split: gate must be [B, Cin] f32')
+    if in_bias is None and in_act is not None:
+        raise ValueError('conv1x1_bias_act_split: in_act needs in_bias')
+    if in_bias is not None and (in_bias.dtype != torch.float32 or in_bias.numel() != K):
+        raise ValueError('conv1x1_bias_act_split: in_bias must be [Cin] f32')
+    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
+                                 or not residual.is_contiguous()):
+        raise ValueError('conv1x1_bias_act_split: residual must be [B, Cout, H, W] like the output, contiguous')
+    if out is None:
+        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
+    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError('conv1x1_bias_act_split: out must be [B, Cout, H, W] like the output, contiguous')
+    check(_lib.load().mtr_conv1x1_bias_act_split(
+        _ptr(x), _ptr(w_split), _ptr(bias.contiguous().float()),
+        None if in_bias is None else _ptr(in_bias.contiguous()), ACT_CODES[in_act],
+        None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act_split')
+    return out

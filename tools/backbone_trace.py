@@ -65,7 +65,7 @@ def record(args):
     net = fold_batchnorm(net.eval(), fused_epilogue=True,
                          dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
                          fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise,
-                         winograd3x3=args.winograd3x3,
+                         winograd3x3=args.winograd3x3, split_gemm=args.split_gemm,
                          deep_projects=args.deep_projects)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
@@ -140,6 +140,8 @@ def _kind(kname):
         return 'K19'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
         return 'K14h'
+    if 'conv1x1_split_kernel' in k:  # K20 (before the generic 'conv' match): the f32 1x1 conv on the bf16 matrix cores
+        return 'K20'
     if 'conv1x1_16_kernel' in k or 'conv1x1_16_deepk_kernel' in k:  # K13h: the 16-bit 1x1 conv + epilogue
         return 'K13h'
     if any(n in k for n in ('conv1x1_kernel', 'conv1x1_deepk_kernel', 'conv1x1_stream_kernel', 'conv1x1_deep64_kernel')):  # K13 (before the 'conv' / 'gemm' matches): the whole 1x1 conv + epilogue
@@ -213,7 +215,7 @@ def _fused_table(per_kernel, pat):
             if col == 'dense conv' and key != 'stem':
                 served[f'{kind}: {kname[:60]}'] += us
         else:
-            col = 'project'   # (K13h, or the library GEMM + K10)
+            col = 'project'   # (K13 / K13h / K20, or the library GEMM + K10)
         b[col] += us
     cols = ['dense conv', 'K14h', 'K19', 'K10', 'project', 'K16h']
     lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project '
@@ -301,13 +303,14 @@ def report(args):
         if role is None:
             # the MBConv layers: '0' expand 1x1, '1' depthwise, '2' SE, '3' project
             role = {0: 'expand', 1: 'depthwise', 2: 'SE other', 3: 'project'}.get(layer, f'layer {layer}')
-            if role == 'project' and kind in ('gemm', 'conv', 'K13', 'K13h'):
+            if role == 'project' and kind in ('gemm', 'conv', 'K13', 'K13h', 'K20'):
                 # (K13 runs inside the ConvBiasAct, the library GEMM inside its .conv)
                 proj[tuple(convs.get(module) or convs.get(module + '.conv', ('?',)))].append(us)
+            # (a layer on K20, `record --split-gemm`, gets its own column: 'expand K20', 'project K20')
             role = role if kind in ('gemm', 'conv', 'K11', 'K18', 'K13', 'K13h') else f'{role} {kind}'
         b[role] += us
     tail_roles = ['SE fc1', 'SE fc1 bias', 'SE act', 'SE fc2', 'SE fc2 bias', 'SE gate fn', 'se_gate', 'x * gate',
-                  'project', 'K10']
+                  'project', 'project K20', 'K10']
     roles = [r for r in tail_roles if any(r in b for b in blocks.values())]
     others = sorted({r for b in blocks.values() for r in b} - set(roles))
     lines = [f'# Backbone per-layer kernel times: {meta.get("backbone", "effnetv2-s")}, batch {meta["batch"]}, '
@@ -368,6 +371,8 @@ def main():
                         'its generic kernel')
     r.add_argument('--winograd3x3', action='store_true',
                    help='fold with winograd3x3=True (f32 only): the dense 3x3 stride-1 layers on K19')
+    r.add_argument('--split-gemm', action='store_true',
+                   help='fold with split_gemm=True (f32 only): the 1x1 stride-1 layers on K20, the split-operand kernel')
     r.add_argument('--deep-projects', action='store_true',
                    help='fold with deep_projects=True (a -copy precision only): the deep project convolutions on '
                         "K13h's deep-K configuration")

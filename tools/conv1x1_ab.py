@@ -23,6 +23,10 @@ The projects of the FusedMBConv blocks an f32 copy arms (FusedMBConv.pre_pair: t
 pass to them) are timed as that hand-over: old = K10 in place on the expanded activation, then K13; new = K13 with
 the input prologue (in_bias, in_act), one launch and one read and one write of the activation less.  --only-pre
 times these classes alone.
+--ab k20 (f32 only) times K13 ('auto', with the prologue where the class has one) against K20
+(kernels.conv1x1_bias_act_split: the same call on the bf16 matrix cores from split operands) per class: HIP graphs of
+--iters calls (default 20 in this mode), --rounds alternated rounds, medians, every round kept, with K20's share of the
+byte floor and of the six-product matrix ceiling (2.5 PF / 6), and the error of both against fp64.
 """
 import argparse
 import json
@@ -56,11 +60,99 @@ def shape_classes(batch, res, backbone='effnetv2-s'):
     return out
 
 
+def k20_ab(args, classes):
+    """The --ab k20 arm: K13 'auto' against K20 per class, both as HIP graph replays."""
+    import torch
+    from metrabs_amd import kernels
+    g = torch.Generator(device='cuda').manual_seed(0)
+    B, rows = args.batch, []
+    med = lambda v: sorted(v)[len(v) // 2]
+    for (K, M, H, W, act, res, gated, pre_act), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+        if args.max_hw is not None and H * W > args.max_hw:
+            continue
+        pre = pre_act is not False
+        x = torch.randn(B, K, H, W, device='cuda', generator=g)
+        w = torch.randn(M, K, 1, 1, device='cuda', generator=g) / K ** 0.5
+        b = torch.randn(M, device='cuda', generator=g)
+        gate = torch.rand(B, K, device='cuda', generator=g) if gated else None
+        r = torch.randn(B, M, H, W, device='cuda', generator=g) if res else None
+        b_in = torch.randn(K, device='cuda', generator=g) if pre else None
+        ws = kernels.pack_conv1x1_split_weight(w)
+        if not (kernels.conv1x1_supported(x, w) and kernels.conv1x1_split_supported(x, ws)):
+            continue
+        y13, y20 = (torch.empty(B, M, H, W, device='cuda') for _ in range(2))
+        kw = dict(gate=gate, residual=r, in_bias=b_in, in_act=pre_act if pre else None)
+        k13 = lambda: kernels.conv1x1_bias_act(x, w, b, act, out=y13, **kw)
+        k20 = lambda: kernels.conv1x1_bias_act_split(x, ws, b, act, out=y20, **kw)
+
+        def captured(fn):
+            st = torch.cuda.Stream()
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                fn()
+                st.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=st, capture_error_mode='thread_local'):
+                    for _ in range(args.iters):
+                        fn()
+            torch.cuda.current_stream().wait_stream(st)
+            torch.cuda.synchronize()
+            return graph
+
+        def timed(graph):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            graph.replay()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
+
+        with torch.inference_mode():
+            k13(), k20()
+            # the error of both against fp64, on the GEMM alone (the first image: enough elements, a small reference)
+            xg = kernels.bias_act_(x[:1].clone(), b_in, pre_act) if pre else x[:1]
+            xg = xg if gate is None else xg * gate[:1, :, None, None]
+            ref = torch.einsum('mk,bkhw->bmhw', w.double().flatten(1), xg.double())
+            zero = torch.zeros_like(b)
+            rms = lambda t: float(((t.double() - ref) ** 2).mean().sqrt() / (ref ** 2).mean().sqrt())
+            e13 = rms(kernels.conv1x1_bias_act(xg, w, zero, None))
+            e20 = rms(kernels.conv1x1_bias_act_split(xg, ws, zero, None))
+            g13, g20 = captured(k13), captured(k20)
+            for _ in range(2):
+                timed(g13), timed(g20)
+            t13, t20 = [], []
+            for _ in range(args.rounds):
+                t13.append(timed(g13))
+                t20.append(timed(g20))
+            del g13, g20
+        flop = 2.0 * B * H * W * K * M
+        byts = 4 * (B * H * W * (K + M * (2 if res else 1))) + 6 * M * K
+        byte_floor = byts / (HBM_TBS * 1e12) * 1e6
+        mfma_floor = flop / (PEAK16_TF / 6 * 1e12) * 1e6
+        row = dict(ab='k20', cin=K, cout=M, hw=f'{H}x{W}', act=act, skip=res, gate=gated, pre_act=pre_act,
+                   layers=len(names), first=names[0], batch=B, res=args.res, backbone=args.backbone, iters=args.iters,
+                   k13_plan=list(kernels.conv1x1_plan(M, K, H * W, B)), k13_us=round(med(t13), 2),
+                   k20_us=round(med(t20), 2), k13_rounds=[round(v, 2) for v in t13],
+                   k20_rounds=[round(v, 2) for v in t20], k20_ahead_every_round=all(n < o for n, o in zip(t20, t13)),
+                   speedup=round(med(t13) / med(t20), 3), byte_floor_us=round(byte_floor, 2),
+                   k20_share_of_byte_floor=round(byte_floor / med(t20), 3), mfma6_floor_us=round(mfma_floor, 2),
+                   k20_share_of_mfma6=round(mfma_floor / med(t20), 3), hbm_tbs=HBM_TBS,
+                   k13_rel_rms=e13, k20_rel_rms=e20)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        for r in rows:
+            f.write(json.dumps(r) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--res', type=int, default=256)
-    ap.add_argument('--iters', type=int, default=50)
+    ap.add_argument('--iters', type=int, default=None, help='calls per timed arm (default 50; 20 with --ab k20)')
+    ap.add_argument('--ab', choices=['k20'], default=None,
+                    help='k20 (f32): K13 as it dispatches against K20, the split-operand kernel, per class')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--dtype', choices=['f32', 'f16', 'bf16'], default='f32')
     ap.add_argument('--backbone', default='effnetv2-s')
@@ -78,7 +170,12 @@ def main():
     import torch
     import torch.nn.functional as F
     from metrabs_amd import kernels
+    args.iters = args.iters or (20 if args.ab else 50)
     classes = shape_classes(args.batch, args.res, args.backbone)
+    if args.ab == 'k20':
+        if args.dtype != 'f32':
+            ap.error('--ab k20 needs --dtype f32')
+        return k20_ab(args, classes)
     dt = {'f32': torch.float32, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype]
     k = 'k13' if dt == torch.float32 else 'k13h'
     peak = PEAK_TF if dt == torch.float32 else PEAK16_TF
