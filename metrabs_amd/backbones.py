@@ -200,14 +200,20 @@ class FusedMBConv(nn.Module):
 
     def _forward_pre(self, x):
         """An armed f32 block.  'k13_pre': the 3x3 convolution alone, then ONE K13 launch that applies its epilogue,
-        the project and the skip.  'k19' (fold_batchnorm(winograd3x3=True)): the 3x3 convolution WITH its epilogue on
-        K19, then the project and the skip on K13.  'chain': what an unarmed block runs.  The tensor without its
-        epilogue never leaves this method, and no tensor passes through two epilogues."""
+        the project and the skip; 'k20_pre': the same launch on K20, where fold_batchnorm(split_gemm=True) armed the
+        project and K20 takes the tensor.  'k19' (fold_batchnorm(winograd3x3=True)): the 3x3 convolution WITH its
+        epilogue on K19, then the project and the skip as an ordinary call of the project layer -- K13, or K20 under
+        split_gemm (the project's own last_path says which).  With K19 switched off or refusing, a
+        WinogradConv3x3BiasAct in pre_pair[0] is the ConvBiasAct it derives from, and the block takes the other
+        branches.  'chain': what an unarmed block runs.  The tensor without its epilogue never leaves this method, and
+        no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the branches with every
+        option on.)"""
         first, project = self.pre_pair
         c = first.conv
         residual = x if self.residual else None
         if isinstance(first, WinogradConv3x3BiasAct) and first.k19_takes(x):
-            # K19 applies the 3x3 layer's own epilogue; the project is then a plain K13 call (no prologue) with the skip
+            # K19 applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
+            # split_gemm; no prologue) with the skip
             self.last_path = 'k19'
             return project(first(x), residual=residual)
         self.last_path = 'chain'
@@ -916,7 +922,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     fuse_blocks=True (needs a 16-bit dtype; off by default) additionally arms every FusedMBConv whose block is
     exactly a Conv3x3BiasAct expand and a ConvBiasAct project without activation: such a block runs as ONE launch
     (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and the chain everywhere
-    else.  The module tree and the state_dict are those of the copy without the option.
+    else (block .last_path 'k16h' / 'chain'; an unarmed block reports None).  The module tree and the state_dict are
+    those of the copy without the option.
     fuse_stem=True (needs fused_epilogue=True; any dtype; off by default; independent of fuse_blocks) makes the stem
     -- the first dense 3x3 stride-2 padding-1 Cin = 3 ConvBiasAct -- a StemConvBiasAct, which runs Preproc, the
     convolution and its epilogue as ONE launch (K17) where that kernel takes the input and the library chain
@@ -943,9 +950,9 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     13 of ResNet-18, none of MobileNetV3.  Such a layer runs Winograd F(2x2, 3x3) on the f32 MFMA with "+ bias", the
     activation and the block's skip in one launch (K19, .last_path 'k19') where that kernel takes the input and the
     shape is not in WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed
-    FusedMBConv expand block runs K19 with its own epilogue and then the project as a plain K13 call (block
-    .last_path 'k19').  Results differ from the default copy's by rounding (both are Winograd evaluations with
-    different summation orders).  The state_dict keys are those of the copy without the option.
+    FusedMBConv expand block runs K19 with its own epilogue and then the project as a plain K13 call -- a plain K20
+    call with split_gemm=True -- (block .last_path 'k19').  Results differ from the default copy's by rounding (both
+    are Winograd evaluations with different summation orders).  The state_dict keys are those of the copy without the option.
     split_gemm=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype; off by default; independent of every other
     option) arms every ConvBiasAct that is 1x1, stride 1, unpadded, ungrouped and emits no mean -- the expand, project
     and head-side 1x1 layers: such a layer runs K20 (.last_path 'k20' / 'k20_gate'; an armed FusedMBConv block reports
@@ -953,7 +960,15 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     bf16 matrix cores, from operands split into three bf16 pieces each and the six largest of the nine cross products,
     with K13's prologue, gate, epilogue and skip.  f32-grade (it passes K13's fp64 bound) but not K13's bits.
     Everything K20 refuses runs exactly today's branch.  A plain attribute on the layers: no module, buffer or
-    state_dict key is added; the split weight is derived state, cached per weight storage and version."""
+    state_dict key is added; the split weight is derived state, cached per weight storage and version.
+    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm; 16-bit:
+    fuse_blocks, fuse_stem, block_depthwise, deep_projects): no two of them arm the same field of the same module, and
+    each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
+    section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
+    module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
+    hand_to are taken after the replacements (WinogradConv3x3BiasAct, Conv3x3BiasAct, StemConvBiasAct); mean_from and
+    gate_to before them, at layers no replacement touches in these networks (those that emit a mean; the 1x1 projects).
+    tests/test_backbone_option_combos_host.py checks every reference of every combination."""
     import copy
     from torch.nn.utils.fusion import fuse_conv_bn_eval
     if backbone.training:
