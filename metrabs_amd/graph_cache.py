@@ -30,7 +30,7 @@ import warnings
 import torch
 
 from metrabs_amd import kernels
-from metrabs_amd.pipeline import CAPTURE_ERROR_MODE
+from metrabs_amd.pipeline import CAPTURE_ERROR_MODE, no_gc_during_capture
 
 
 class FrameSet:
@@ -157,7 +157,7 @@ class BatchGraph:
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             kw = {} if pool is None else dict(pool=pool)
-            with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_ERROR_MODE, **kw):
+            with no_gc_during_capture(), torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_ERROR_MODE, **kw):
                 self.out = body()
         # tensors outside the graph's pool that the captured kernels read by address: the head's derived
         # weights (packed tiles, the latent prefix's rows).  Holding them keeps the allocator from handing

@@ -3,6 +3,9 @@ rotation, i.e. Pose3dEstimator._predict_single_batch (multiperson_model.py:227-2
 already on the GPU and no host synchronisation, so that one internal batch can be captured into a
 HIP graph (launch-bound at 64 crops: ~10 kernels of ours + the backbone's).
 """
+import contextlib
+import gc
+
 import torch
 
 from metrabs_amd import kernels
@@ -14,6 +17,25 @@ from metrabs_amd import kernels
 # process down (seen once in four one-rank RCCL runs of bench.py --graph-gather, round 4).  Thread-local mode
 # only polices the capturing thread, which is the one that has to behave.
 CAPTURE_ERROR_MODE = 'thread_local'
+
+
+@contextlib.contextmanager
+def no_gc_during_capture():
+    """Around every stream capture of this package: collect now, then keep Python's cyclic collector off until the
+    capture has ended.  A captured body allocates thousands of objects, so an automatic collection can fall into the
+    capture -- on the capturing thread.  If it then finds a dead estimator (they sit in reference cycles, so only the
+    collector frees them) it destroys that estimator's torch.cuda.CUDAGraph objects, whose destructor calls
+    hipGraphExecDestroy / hipGraphDestroy: not permitted on a thread that is capturing, and an error in a destructor
+    ends the process (abort).  When a collection falls depends on every allocation since the interpreter started,
+    so the same code passes or aborts with the length of an imported module."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def predict_single_batch(crop_model, mirror_mapping, should_flip, any_flip, pyramid, intrinsic_matrix,
@@ -103,7 +125,7 @@ class GraphedCropPipeline:
             torch.cuda.synchronize()
             if self.use_graph:
                 self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_ERROR_MODE):
+                with no_gc_during_capture(), torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_ERROR_MODE):
                     self.poses = self._body()
         return self
 

@@ -803,3 +803,212 @@ def head_weights_as_consumed(w, feat_dtype):
     if feat_dtype == torch.float32:
         return w
     return w.to(feat_dtype).float()
+
+
+# ------------------------------------------------------------------ post-head kernels (K5, K7, K8) on the paths
+# the parity cases above do not reach: tests/test_posthead_cases_host.py checks the properties of these
+# cases on the CPU, tests/test_gpu_reconstruct_paths.py, test_gpu_postprocess_boxes.py and test_gpu_filter.py
+# run them through the kernels.
+
+# (B, J): either side of the one-launch limit of mtr_reconstruct_absolute (B * J <= 16384)
+RECON_PATH_SHAPES = {
+    'b1030_j16': (1030, 16),    # 16 480: moments grid-stride (> 1024 crops), > 64 partial rows, B % 4 != 0
+    'b65_j253': (65, 253),      # 16 445: J > 64 and J % 64 != 0
+    'b128_j128': (128, 128),    # 16 384: the last shape of the one-launch kernel
+    'b4097_j4': (4097, 4),      # 16 388: just over the limit with a tiny J
+}
+RECON_GENERAL_K_SHAPE = (300, 55)   # 16 500
+
+
+def recon_paths_case(B, J, seed, general_k=False, mix_3d_inside_fov=0.5, centered_stride=True):
+    """Synthetic consistent poses as tests/test_gpu_fuzz.py::test_reconstruct_fuzz builds them: a reference point
+    2 - 4 m deep, a relative pose around it, its projection plus 2 px of noise; about three quarters of the joints
+    land inside the FOV band.  general_k: skew, K[1,0] = 0.2 and a bottom row [g, h, 1] (inverse_rows01 of K5 is
+    written for a general 3x3; every other case has [0, 0, 1]).
+    -> (coords2d [B,J,2], coords3d_rel [B,J,3], K [B,3,3], cfg, ref [B,3])"""
+    cfg = HeadConfig(centered_stride=centered_stride)
+    cfg.mix_3d_inside_fov = mix_3d_inside_fov
+    g = gen(seed)
+    P = cfg.proc_side
+    f = 450 + 100 * torch.rand(B, generator=g)
+    K = torch.zeros(B, 3, 3)
+    K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = f, f * 1.01, P / 2, P / 2 + 1, 1
+    K[:, 0, 1] = 0.3
+    if general_k:
+        K[:, 1, 0] = 0.2
+        K[:, 2, 0] = RECON_GENERAL_K_BOTTOM[0] * (0.5 + torch.rand(B, generator=g))
+        K[:, 2, 1] = RECON_GENERAL_K_BOTTOM[1] * (0.5 + torch.rand(B, generator=g))
+    ref = torch.stack([150 * torch.randn(B, generator=g), 150 * torch.randn(B, generator=g),
+                       2000 + 2000 * torch.rand(B, generator=g)], dim=1)
+    rel = torch.randn(B, J, 3, generator=g) * torch.tensor([300.0, 400.0, 250.0])
+    abs3d = rel + ref[:, None]
+    c2d = (abs3d[..., :2] / abs3d[..., 2:]) * f[:, None, None] + P / 2 + 2 * torch.randn(B, J, 2, generator=g)
+    return c2d.contiguous(), rel.contiguous(), K, cfg, ref
+
+
+# (g, h) of the general-K case, each times a factor in 0.5 .. 1.5 per crop.  (1e-5 moves the fp64 answer by 2 bounds of
+# tests/test_gpu_reconstruct_paths.py at the median joint; the case must move it by > 100: test_posthead_cases_host.py)
+RECON_GENERAL_K_BOTTOM = (1e-3, -1e-3)
+
+
+def f32_ulp_at(x):
+    """Spacing of float32 at |x| (x float64): 2^(e - 24) for |x| = m 2^e, 0.5 <= m < 1."""
+    _, e = torch.frexp(x.double().abs().clamp_min(2.0 ** -126))
+    return torch.ldexp(torch.ones_like(x, dtype=torch.float64), e - 24)
+
+
+def recon_ulp_bound(out64, ref64):
+    """The bound of tests/test_gpu_reconstruct_paths.py on |K5 - fp64| per joint, [B, J, 1]: 2 ulp of float32 at the
+    joint's largest absolute coordinate + 0.5 ulp at the larger of that and the reference point's largest absolute
+    coordinate -- 2.5 ulp at the joint wherever the reference point is no larger than the joint (derivation there)."""
+    mj = out64.abs().amax(dim=-1, keepdim=True)
+    mr = ref64.abs().amax(dim=-1)[:, None, None].expand_as(mj)
+    return 2.0 * f32_ulp_at(mj) + 0.5 * f32_ulp_at(torch.maximum(mj, mr))
+
+
+def recon_candidates_fp64(coords2d, coords3d_rel, intrinsics, cfg, mix_3d_inside_fov='cfg', weak_perspective=False):
+    """The pieces of cpu_ref.reconstruct_absolute in float64: -> dict(ref [B,3], normalized [B,J,2],
+    abs_3d_based = rel + ref, abs_2d_based = the back-projection (mixed when the mix is on), in_fov [B,J],
+    out = what reconstruct_absolute returns)."""
+    from oracle import cpu_ref
+    if mix_3d_inside_fov == 'cfg':
+        mix_3d_inside_fov = cfg.mix_3d_inside_fov
+    c2d, rel = coords2d.double(), coords3d_rel.double()
+    inv_k = torch.linalg.inv(intrinsics.double())
+    normalized = (cpu_ref.to_homogeneous(c2d) @ inv_k.transpose(1, 2))[..., :2]
+    in_fov = cpu_ref.is_within_fov(c2d, cfg)
+    if weak_perspective:
+        ref = cpu_ref.reconstruct_ref_weakpersp(normalized, rel, in_fov)
+    else:
+        ref = cpu_ref.reconstruct_ref_fullpersp(normalized, rel, in_fov)
+    abs3 = rel + ref[:, None]
+    abs2 = cpu_ref.back_project(normalized, rel[..., 2], ref[:, 2])
+    if mix_3d_inside_fov is not None:
+        abs2 = mix_3d_inside_fov * abs3 + (1 - mix_3d_inside_fov) * abs2
+    return dict(ref=ref, normalized=normalized, abs_3d_based=abs3, abs_2d_based=abs2, in_fov=in_fov,
+                out=torch.where(in_fov[..., None], abs2, abs3))
+
+
+def recon_fov_edges_case(centered_stride):
+    """A small consistent batch (no mixing) in which crop b's joints 0 .. 11 sit ON the FOV band's edges: x (joints
+    0 - 5) or y (6 - 11) is exactly `lower`, the float32 next below it, the next above it, exactly `upper`, the next
+    above and the next below; the other coordinate is mid-image.  is_within_fov is x >= lower && x <= upper.
+    -> (coords2d, coords3d_rel, K, cfg, lower, upper, expect_inside [B,J] bool for the 12 edge joints (others: the
+    oracle's own mask), edge_joints = 12)"""
+    c2d, rel, K, cfg, _ = recon_paths_case(6, 17, 8800 + int(centered_stride), mix_3d_inside_fov=None,
+                                           centered_stride=centered_stride)
+    offset = 0.0 if centered_stride else -cfg.stride_train / 2
+    lower = cfg.stride_train * 0.75 + offset
+    upper = cfg.proc_side - cfg.stride_train * 0.75 + offset
+    lo, up = torch.tensor(lower, dtype=torch.float32), torch.tensor(upper, dtype=torch.float32)
+    inf = torch.tensor(float('inf'))
+    values = [lo, torch.nextafter(lo, -inf), torch.nextafter(lo, inf), up, torch.nextafter(up, inf),
+              torch.nextafter(up, -inf)]
+    inside = [True, False, True, True, False, True]
+    B = len(c2d)
+    from oracle import cpu_ref
+    expect = cpu_ref.is_within_fov(c2d, cfg).clone()
+    for b in range(B):
+        mid = 100.0 + 7.0 * b
+        for k, v in enumerate(values):
+            c2d[b, k] = torch.stack([v, torch.tensor(mid)])
+            c2d[b, 6 + k] = torch.stack([torch.tensor(mid), v])
+            expect[b, k] = expect[b, 6 + k] = inside[k]
+    return c2d.contiguous(), rel, K, cfg, lower, upper, expect, 12
+
+
+def pair_swap_mapping(J):
+    """A mirror mapping that is not the identity for any joint count: 2i <-> 2i + 1 (a last odd joint maps to
+    itself)."""
+    m = torch.arange(J)
+    even = torch.arange(0, J - 1, 2)
+    m[even], m[even + 1] = even + 1, even
+    return m
+
+
+def per_box_cameras(n, seed):
+    """K7 inputs that differ for every box of one call: extrinsics (rotation and translation), intrinsics and
+    distortion -- box 0 none, box 1 DISTORTION_5, box 2 DISTORTION_12, cycling, each scaled per box so that no
+    two boxes share a vector.  -> (K [n,3,3], distortion [n,12], extrinsics [n,4,4])"""
+    g = gen(seed)
+    K = torch.stack([intrinsics_for(1080, 1920, 55.0, seed + 31 * i) for i in range(n)])
+    K[:, 0, 0] *= 0.8 + 0.4 * torch.rand(n, generator=g)
+    K[:, 1, 1] *= 0.8 + 0.4 * torch.rand(n, generator=g)
+    K[:, :2, 2] += 40 * torch.randn(n, 2, generator=g)
+    d = torch.zeros(n, 12)
+    for b in range(n):
+        if b % 3 == 1:
+            d[b, :5] = torch.tensor(DISTORTION_5) * (1 + 0.25 * b)
+        elif b % 3 == 2:
+            d[b] = torch.tensor(DISTORTION_12) * (1 + 0.25 * b)
+    w = 0.3 * torch.randn(n, 3, generator=g)
+    zero = torch.zeros(n)
+    skew = torch.stack([torch.stack([zero, -w[:, 2], w[:, 1]], -1), torch.stack([w[:, 2], zero, -w[:, 0]], -1),
+                        torch.stack([-w[:, 1], w[:, 0], zero], -1)], -2)
+    E = torch.eye(4).repeat(n, 1, 1)
+    E[:, :3, :3] = torch.linalg.matrix_exp(skew)
+    E[:, :3, 3] = 500 * torch.randn(n, 3, generator=g)
+    return K, d, E
+
+
+def filter_grid_case(counts, A, J, seed, dup=(5, 4, 1), box_ok=(1, 0), scores=None, cols=32):
+    """K8 inputs as tests/test_gpu_filter.py::test_filter_sizes_beyond_the_common_ones builds them, for several images
+    and with the duplicates and the box test placed by rule: people on a grid 2.5 m x 3 m apart at 9 m (similarity 0
+    between any two), 2 mm of noise per augmentation; pose i of an image is an exact duplicate (other noise) of pose
+    i - dup[2] when i % dup[0] == dup[1]; a pose whose index is not box_ok[1] modulo box_ok[0] gets a detection box
+    three box widths away (it fails is_pose_consistent_with_box and is invalid).  Scores: 0.9 - 0.0005 i (a
+    duplicate scores below its original), or scores[image][i].  Decisions sit far from every threshold.
+    -> dict(boxes, poses3d, poses2d: lists per image; edges, mean_bones, n_joints)"""
+    g = gen(seed)
+    edges = [(i, i + 1) for i in range(J - 1)]
+    template = torch.cumsum(torch.randn(J, 3, generator=g) * torch.tensor([60.0, 90.0, 40.0]), dim=0)
+    tj = torch.tensor(edges)
+    mean_bones = torch.norm(template[tj[:, 0]] - template[tj[:, 1]], dim=-1)
+    boxes, poses3d, poses2d = [], [], []
+    for im, n in enumerate(counts):
+        bases = []
+        for i in range(n):
+            base = template + torch.tensor([(i % cols) * 2500.0 - 1250.0 * cols, (i // cols) * 3000.0, 9000.0])
+            if i % dup[0] == dup[1] and i >= dup[2]:
+                base = bases[i - dup[2]].clone()
+            bases.append(base)
+        if n == 0:
+            boxes.append(torch.zeros(0, 5)); poses3d.append(torch.zeros(0, A, J, 3)); poses2d.append(torch.zeros(0, A, J, 2))
+            continue
+        p3 = torch.stack(bases)[:, None].repeat(1, A, 1, 1) + torch.randn(n, A, J, 3, generator=g) * 2.0
+        p2 = 1500.0 * p3[..., :2] / p3[..., 2:] + torch.tensor([960.0, 540.0])
+        m2 = p2.mean(1)
+        lo, hi = m2.min(1).values, m2.max(1).values
+        sc = torch.tensor(scores[im], dtype=torch.float32) if scores is not None else 0.9 - 0.0005 * torch.arange(n)
+        pad = 0.05 * (hi - lo)   # the pose's box covers 83 % of its detection: far above the 50 % of the box test
+        bx = torch.cat([lo - pad, hi - lo + 2 * pad, sc[:, None]], dim=1)
+        off = (torch.arange(n) % box_ok[0]) != box_ok[1]
+        bx[off, 0] += 3 * bx[off, 2]
+        boxes.append(bx.float()); poses3d.append(p3.float()); poses2d.append(p2.float())
+    return dict(boxes=boxes, poses3d=poses3d, poses2d=poses2d, edges=edges, mean_bones=mean_bones, n_joints=J)
+
+
+def filter_over256_case():
+    """One image of 300 poses, J = 17, A = 2, every fifth a duplicate: 240 valid survivors of the NMS -- the
+    256-thread strides of K8's rank and suppression passes take a second step (300 valid poses)."""
+    return filter_grid_case([300], 2, 17, 9101)
+
+
+def filter_cap_case():
+    """One image of 200 poses, every fifth a duplicate: 160 distinct survivors, more than the cap of 150."""
+    return filter_grid_case([200], 2, 17, 9102)
+
+
+def filter_ties_case():
+    """Equal scores on distinct poses and on exact duplicates (pose 4 duplicates 3, 9 duplicates 8): the lower index
+    ranks first, as in the oracle's stable argsort."""
+    scores = [[0.5, 0.7, 0.5, 0.6, 0.6, 0.5, 0.7, 0.7, 0.5, 0.5, 0.9, 0.5]]
+    return filter_grid_case([12], 2, 17, 9103, scores=scores)
+
+
+def filter_full_table_case():
+    """Image 0 fills K8's per-image tables: 1024 poses, of which every eighth (i % 8 == 7, so index 1023 too) passes
+    the box test -- 128 valid; pose i with i % 16 == 7 duplicates pose i - 8 (valid as well, higher score).  Image 1
+    (24 poses by the same rules: 7, 15 and 23 valid, 23 a duplicate of 15) lies behind it, so its row_start and
+    similarity offset follow a full table."""
+    return filter_grid_case([1024, 24], 2, 17, 9104, dup=(16, 7, 8), box_ok=(8, 7))

@@ -102,6 +102,24 @@ def test_linear_combine_points_kernel(shape, hip_lib):
     assert torch.equal(eye, pts)
 
 
+def test_linear_combine_points_at_the_latent_limit(hip_lib):
+    """J_in = 4096 latent points fill the kernel's 48 KiB of LDS: runs, within 1 ulp of the float64 einsum; 4097 is
+    refused (MTR_E_SHAPE) with no launch."""
+    from metrabs_amd import kernels
+    g = cases.gen(79)
+    pts = torch.randn(2, 4096, 3, generator=g) * 800 + torch.tensor([0.0, 0.0, 3500.0])
+    w = torch.randn(4096, 3, generator=g) / 64
+    out = kernels.linear_combine_points(pts.cuda(), w.cuda()).cpu()
+    want64 = torch.einsum('bjc,jJ->bJc', pts.double(), w.double())
+    spacing = (torch.nextafter(out.abs(), torch.full_like(out, float('inf'))) - out.abs()).double()
+    assert out.shape == (2, 3, 3) and bool(((out.double() - want64).abs() <= spacing).all())
+    poisoned = torch.full((2, 3, 3), float('nan'), device='cuda')
+    with pytest.raises(RuntimeError, match=r'code -2'):
+        kernels.linear_combine_points(torch.zeros(2, 4097, 3, device='cuda'), torch.zeros(4097, 3, device='cuda'), out=poisoned)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(poisoned).all())
+
+
 def test_estimator_over_a_latent_model_with_graphs(hip_lib):
     """The latent crop model behind Pose3dEstimator (eager, then captured): one more launch inside the body,
     same results either way, and equal to the oracle's estimate_poses_batched over the oracle's latent model."""

@@ -191,3 +191,39 @@ def test_backbone_fingerprint_sees_the_backbone_alone_being_cast_moved_or_replac
     model.backbone = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 1))
     assert graph_cache.backbone_fingerprint(model)[0] != fp[0]
     assert graph_cache.backbone_fingerprint(types.SimpleNamespace(backbone=lambda x: x))   # (a callable stub: its identity)
+
+
+def test_the_cyclic_collector_stays_out_of_a_capture():
+    """pipeline.no_gc_during_capture (around both captures of the package): dead cycles are collected BEFORE the
+    capture -- an estimator and its graph cache refer to each other, so only the collector destroys a dead estimator's
+    graphs, and it must not do that on a thread that is capturing --, the collector is off inside and back afterwards
+    (also after an exception), and a collector the caller had switched off stays off."""
+    import gc
+    import inspect
+    import weakref
+    from metrabs_amd import pipeline
+
+    class Node:
+        pass
+
+    a, b = Node(), Node()
+    a.other, b.other = b, a          # as Pose3dEstimator.graphs <-> GraphCache.est
+    dead = weakref.ref(a)
+    del a, b
+    assert gc.isenabled()
+    with pipeline.no_gc_during_capture():
+        assert dead() is None and not gc.isenabled()
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with pipeline.no_gc_during_capture():
+            raise RuntimeError('capture failed')
+    assert gc.isenabled()
+    gc.disable()
+    try:
+        with pipeline.no_gc_during_capture():
+            pass
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
+    for fn in (graph_cache.BatchGraph.__init__, pipeline.GraphedCropPipeline.capture):
+        assert 'with no_gc_during_capture(), torch.cuda.graph(' in inspect.getsource(fn)
