@@ -1,8 +1,10 @@
 """Plain-torch.nn restatements of the reference's backbones, random-initialised, for the synthetic
 benchmark workloads of BASELINE.json (torchvision is not in this image and there is no network for
-checkpoints).  The backbone is NOT part of the hand-written hot path: it stays on PyTorch-ROCm
-(MIOpen / rocBLAS), as the north star prescribes.  Only output shape matters to the path:
-[B, C, P/32, P/32] with C = 1280 (EffNetV2-S/L, MobileNetV3-L) or 512 (ResNet-18).
+checkpoints).  The networks as built here run on PyTorch-ROCm (MIOpen / rocBLAS); the inference copy that
+fold_batchnorm makes of one is part of the hand-written hot path: its folded layers (ConvBiasAct and the classes beside
+it, below) run the HIP kernels K10 to K20 of kernels.py wherever one takes the tensor, and the library everywhere else.
+Each folded layer decides that once per forward, in its path().  Only the output shape matters
+to what follows: [B, C, P/32, P/32] with C = 1280 (EffNetV2-S/L, MobileNetV3-L) or 512 (ResNet-18).
 
 Architecture tables follow metrabs_pytorch/backbones/efficientnet.py:379-435 (EfficientNetV2 S/L:
 FusedMBConv/MBConv stages, SE ratio 0.25, BN eps 1e-3, PreprocLayer x*2-1 :1181-1186),
@@ -16,6 +18,8 @@ import threading
 import torch
 import torch.nn.functional as F
 from torch import nn
+
+from . import _lib, kernels
 
 
 class DepthwiseConv2d(nn.Conv2d):
@@ -70,7 +74,7 @@ class SqueezeExcite(nn.Module):
     # epilogue pass also produced the per-channel mean of the tensor it handed over
     mean_from = ()
     # set by fold_batchnorm(fused_epilogue=True): the ConvBiasAct of the block's project conv, which
-    # applies the gate to its input itself when it runs on K13
+    # applies the gate to its input itself where one of its 1x1 kernels takes the tensor (ConvBiasAct.applies_gate)
     gate_to = ()
 
     _GATE_NAMES = {nn.Sigmoid: 'sigmoid', nn.Hardsigmoid: 'hardsigmoid'}
@@ -81,16 +85,15 @@ class SqueezeExcite(nn.Module):
             mean = src.take_mean_f32(x)
         if mean is not None and self._fused_gate_ok():
             # fc1, + b1, act, fc2, + b2, gate as ONE HIP launch from the f32 mean (K12)
-            from . import kernels
             g = kernels.se_gate(mean, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
                                 _ACT_NAMES[type(self.act)], self._GATE_NAMES[type(self.gate)], w2t=self._fc2_wt())
             for dst in self.gate_to:
-                if dst.k13_takes(x) or dst.k13h_takes(x) or dst.k13h_deep_takes(x):
-                    # the project conv (K13 / K13h) multiplies x by the gate as it stages x: no x * g pass
+                if dst.applies_gate(x):
+                    # the project conv multiplies x by the gate as it stages x: no x * g pass
                     dst.give_gate(x, g)
                     return x
             return x * g.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
-        if x.dtype != self.fc1.weight.dtype and not torch.is_autocast_enabled(x.device.type):
+        if x.dtype != self.fc1.weight.dtype and _autocast_off(x.device.type):
             return self._forward_16bit_copy(x, mean)
         s = None if mean is None else mean.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
         if s is None:
@@ -108,18 +111,15 @@ class SqueezeExcite(nn.Module):
 
     def _fc2_wt(self):
         """fc2's weight transposed to [S, C] for K12 (a wave's fc2 loads are then contiguous): made on the first
-        fused forward and again whenever the weight has moved or been written since (not part of the state dict)."""
-        w = self.fc2.weight
-        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
-        if self._w2t is None or self._w2t[0] != key:
-            self._w2t = (key, w.detach().reshape(w.shape[0], -1).t().contiguous())
+        fused forward and kept as _derived_weight says."""
+        self._w2t = _derived_weight(self._w2t, self.fc2.weight,
+                                    lambda w: w.detach().reshape(w.shape[0], -1).t().contiguous())
         return self._w2t[1]
 
     def _fused_gate_ok(self):
         """K12 computes no gradient: only where none is wanted, for the layer types it implements."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return False
-        return (type(self.act) in (nn.SiLU, nn.ReLU) and type(self.gate) in self._GATE_NAMES
+        return (_no_grad_wanted(self.parameters())
+                and type(self.act) in (nn.SiLU, nn.ReLU) and type(self.gate) in self._GATE_NAMES
                 and self.fc1.weight.dtype == torch.float32 and self.fc1.bias is not None
                 and self.fc2.bias is not None and self.fc1.weight.is_cuda
                 and self.fc1.in_channels % 4 == 0)
@@ -180,11 +180,10 @@ class FusedMBConv(nn.Module):
         w3, w1 = expand.conv.weight, project.conv.weight
         if x.dtype != w3.dtype or w1.dtype != w3.dtype or x.dtype not in (torch.float16, torch.bfloat16):
             return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (w3.requires_grad or w1.requires_grad)):
+        if not _inference_call(w3, w1):
             return False
         if (w3.shape[1], w3.shape[0], w1.shape[0], expand.stride, x.shape[2], x.shape[3]) in FusedMBConv.k16h_slower:
             return False
-        from . import kernels
         return kernels.fused_mbconv16_supported(x, expand.weight_packed, w1, expand.stride)
 
     # set by fold_batchnorm(fused_epilogue=True) on an f32 copy: (the block's 3x3 ConvBiasAct, its project
@@ -205,36 +204,35 @@ class FusedMBConv(nn.Module):
         epilogue on K19, then the project and the skip as an ordinary call of the project layer -- K13, or K20 under
         split_gemm (the project's own last_path says which).  With K19 switched off or refusing, a
         WinogradConv3x3BiasAct in pre_pair[0] is the ConvBiasAct it derives from, and the block takes the other
-        branches.  'chain': what an unarmed block runs.  The tensor without its epilogue never leaves this method, and
-        no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the branches with every
-        option on.)"""
+        branches.  'chain': what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
+        nothing for them; the tensor without its epilogue goes to the project alone, which applies that epilogue on
+        every path, and no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the
+        branches with every option on.)"""
         first, project = self.pre_pair
         c = first.conv
         residual = x if self.residual else None
-        if isinstance(first, WinogradConv3x3BiasAct) and first.k19_takes(x):
+        if isinstance(first, WinogradConv3x3BiasAct) and first.path(x) == 'k19':
             # K19 applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
             # split_gemm; no prologue) with the skip
             self.last_path = 'k19'
             return project(first(x), residual=residual)
         self.last_path = 'chain'
         if not (FusedMBConv.use_k13_pre and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
-                and c.weight.dtype == torch.float32 and not torch.is_autocast_enabled('cuda')
-                and not (torch.is_grad_enabled() and (c.weight.requires_grad or x.requires_grad))
+                and c.weight.dtype == torch.float32 and _inference_call(c.weight, x=x)
                 and (c.in_channels, c.out_channels, project.conv.out_channels, c.stride[0], x.shape[2], x.shape[3])
                 not in FusedMBConv.k13_pre_slower):
             return _block_plus_skip(self.block, x) if self.residual else self.block(x)
-        y = first(x, defer_epilogue=True)
-        if project.k13_accepts(y, residual):  # (fold_batchnorm(split_gemm=True): the same launch on K20 where it takes y)
-            self.last_path = 'k20_pre' if project.k20_takes(y) else 'k13_pre'
-            return project(y, residual=residual, pre=first)
-        return project(_finish_bias_act(first, y, None), residual=residual)
+        y = project(first(x, defer_epilogue=True), residual=residual, pre=first)
+        # (fold_batchnorm(split_gemm=True): the same launch on K20 where it takes the tensor; a project that refuses
+        # ran K10 and its own library path: the chain)
+        self.last_path = {'k13': 'k13_pre', 'k20': 'k20_pre'}.get(project.last_path, 'chain')
+        return y
 
     def forward(self, x):
         if self.pre_pair:
             return self._forward_pre(x)
         if self.fused_pair:
             if self.k16h_takes(x):
-                from . import kernels
                 expand, project = self.fused_pair
                 self.last_path = 'k16h'
                 return kernels.fused_mbconv16(x, expand.weight_packed, expand.bias, expand.act_name, expand.stride,
@@ -388,6 +386,64 @@ def build_backbone(name):
 
 
 _ACT_NAMES = {nn.SiLU: 'silu', nn.ReLU: 'relu', nn.Hardswish: 'hardswish'}
+_16BIT = (torch.float16, torch.bfloat16)
+_FLOATS = (torch.float32,) + _16BIT
+
+
+# ---- what the folded layers below ask of a call, a convolution, a skip connection: each question written once
+
+def _autocast_off(device_type='cuda'):
+    return not torch.is_autocast_enabled(device_type)
+
+
+def _no_grad_wanted(tensors):
+    """No hand-written kernel computes a gradient: they run only where none is wanted for `tensors` (an iterable, looked
+    at in grad mode alone)."""
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+
+
+def _inference_call(*weights, x=None):
+    """An inference call: autocast off, and no gradient wanted for these weights -- nor for the input, where the caller
+    passes it as `x` (K17, K19 and the K13 prologue do; K13, K13h, K14h, K16h and K20 look at their weights alone)."""
+    return _autocast_off() and _no_grad_wanted(weights if x is None else weights + (x,))
+
+
+def _plain_1x1(conv):
+    """A plain 1x1 convolution: stride 1, unpadded, undilated, ungrouped, without a bias of its own (folded layers keep
+    theirs beside the conv)."""
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
+
+
+def _dense_3x3(conv, strides):
+    """A dense 3x3, padding-1 convolution with one of `strides`: what K14h, K17 and K19 are written for."""
+    return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
+            and conv.dilation == (1, 1) and conv.stride in strides and conv.padding == (1, 1)
+            and conv.padding_mode == 'zeros')
+
+
+def _addable(residual, x, shape=None):
+    """Whether a kernel's epilogue can add `residual` to a result like `x`: none at all, or x's dtype, contiguous and
+    16-byte aligned -- and of `shape`, where the caller knows the result's (K19 does; the others leave the shape to
+    the kernels.py wrapper, which raises)."""
+    return residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
+                                and (shape is None or residual.shape == shape) and residual.data_ptr() % 16 == 0)
+
+
+def _to_copy_dtype(x, weight):
+    """The first convolution of a 16-bit copy casts its input, once: `x` in the dtype of `weight` (autocast off)."""
+    if x.dtype != weight.dtype and weight.dtype in _16BIT and _autocast_off(x.device.type):
+        return x.to(weight.dtype)
+    return x
+
+
+def _derived_weight(slot, w, make):
+    """A tensor derived from the weight `w` (transposed, split, transformed: no part of the state dict), kept in a slot
+    that is None or (key, tensor): -> the slot to keep, with make(w) made anew whenever the weight has moved or been
+    written since.  An inference tensor carries no version counter: after writing such a weight in place, set the
+    slot to None."""
+    key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
+    return slot if slot is not None and slot[0] == key else (key, make(w))
 
 
 class ConvBiasAct(nn.Module):
@@ -415,25 +471,22 @@ class ConvBiasAct(nn.Module):
     # since 1536 -> 256 on 8x8 maps runs K13's 'deep64' tiles
     k13_slower = frozenset()
 
+    def _plain_1x1_call(self, x, c):
+        """What K13, K13h and K20 all ask: a plain 1x1 layer (`c`, its conv: a submodule is looked up once per
+        question) that emits no mean, a CUDA [B, C, H, W] input, an inference call."""
+        return not self.emit_mean and x.is_cuda and x.dim() == 4 and _plain_1x1(c) and _inference_call(c.weight)
+
     def k13_takes(self, x):
         """Whether forward(x) runs on K13 (conv1x1.hip): a 1x1 stride-1 unpadded ungrouped conv on an f32
         CUDA NCHW-contiguous input, autocast off, no gradient wanted, a shape the C entry accepts."""
         c = self.conv
-        if not (ConvBiasAct.use_k13 and not self.emit_mean and x.is_cuda and c.kernel_size == (1, 1)
-                and c.stride == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1
-                and c.bias is None and c.padding_mode == 'zeros'):
-            return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
-            return False
-        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k13_slower:
-            return False
-        from . import kernels
-        return kernels.conv1x1_supported(x, c.weight)
+        return (ConvBiasAct.use_k13 and self._plain_1x1_call(x, c)
+                and (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) not in ConvBiasAct.k13_slower
+                and kernels.conv1x1_supported(x, c.weight))
 
     def k13_accepts(self, x, residual):
         """k13_takes(x), and a skip connection K13's epilogue can add: x's dtype, contiguous, 16-byte aligned."""
-        return self.k13_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                                           and residual.data_ptr() % 16 == 0))
+        return self.k13_takes(x) and _addable(residual, x)
 
     # fold_batchnorm(split_gemm=True) sets this on the 1x1, stride-1, unpadded, ungrouped layers of an f32 copy that emit
     # no mean: they run K20 (conv1x1_split.hip, the product on the bf16 matrix cores from split operands) wherever K13
@@ -452,27 +505,24 @@ class ConvBiasAct(nn.Module):
 
     def weight_split(self):
         """The conv's weight split for K20 ([3, Cout, Kp] bf16, kernels.pack_conv1x1_split_weight): made on the first
-        K20 forward and again whenever the weight has moved or been written since (not part of the state dict).  An
-        inference tensor carries no version counter (as WinogradConv3x3BiasAct.weight_u): set self._ws = None after
-        writing such a weight in place."""
-        w = self.conv.weight
-        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
-        if self._ws is None or self._ws[0] != key:
-            from . import kernels
-            self._ws = (key, kernels.pack_conv1x1_split_weight(w))
+        K20 forward and kept as _derived_weight says."""
+        self._ws = _derived_weight(self._ws, self.conv.weight, kernels.pack_conv1x1_split_weight)
         return self._ws[1]
 
+    def _k20_for_k13(self, x):
+        """Whether an input that K13 takes goes to K20 instead: an armed layer, the switch on, a shape the C entry
+        accepts and that is not listed as slower."""
+        if not (self.split_gemm and ConvBiasAct.use_k20):
+            return False
+        c, hw = self.conv, x.shape[2] * x.shape[3]
+        return ((c.in_channels, c.out_channels, hw) not in ConvBiasAct.k20_slower
+                and _lib.load().mtr_conv1x1_split_supported(x.shape[0], c.out_channels, c.in_channels, hw) == 0)
+
     def k20_takes(self, x):
-        """Whether forward(x) runs on K20: an armed layer, the switch on, everything k13_takes(x) asks for, a shape the
-        C entry accepts and that is not listed as slower, no gradient wanted for x either."""
-        if not (self.split_gemm and ConvBiasAct.use_k20 and self.k13_takes(x)):
-            return False
-        c = self.conv
-        if (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in ConvBiasAct.k20_slower:
-            return False
-        from . import _lib
-        return _lib.load().mtr_conv1x1_split_supported(x.shape[0], c.out_channels, c.in_channels,
-                                                       x.shape[2] * x.shape[3]) == 0
+        """Whether forward(x) runs on K20: an armed layer, the switch on, everything k13_takes(x) asks for (so no
+        gradient wanted for the weight; like K13 it does not look at x.requires_grad), a shape the C entry accepts and
+        that is not listed as slower."""
+        return self.split_gemm and self.k13_takes(x) and self._k20_for_k13(x)
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions of a 16-bit copy on K13h instead of
     # rocBLAS + K10 (+ x * gate)
@@ -492,17 +542,9 @@ class ConvBiasAct(nn.Module):
 
     def _k13h_takes(self, x, slower):
         c = self.conv
-        if not (ConvBiasAct.use_k13h and not self.emit_mean and x.is_cuda and x.dtype == c.weight.dtype
-                and x.dtype in (torch.float16, torch.bfloat16) and c.kernel_size == (1, 1)
-                and c.stride == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1
-                and c.bias is None and c.padding_mode == 'zeros'):
-            return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
-            return False
-        if x.dim() != 4 or (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) in slower:
-            return False
-        from . import kernels
-        return kernels.conv1x1_16_supported(x, c.weight)
+        return (ConvBiasAct.use_k13h and x.dtype in _16BIT and x.dtype == c.weight.dtype and self._plain_1x1_call(x, c)
+                and (c.in_channels, c.out_channels, x.shape[2] * x.shape[3]) not in slower
+                and kernels.conv1x1_16_supported(x, c.weight))
 
     # fold_batchnorm(deep_projects=True) sets this on the deep project convolutions of a 16-bit copy (1x1, stride 1,
     # ungrouped, no activation, Cin >= 768, Cout > 160): they run K13h in `deep_config` wherever K13h takes the input,
@@ -518,6 +560,33 @@ class ConvBiasAct(nn.Module):
         """Whether forward(x) runs on K13h in `deep_config`: an armed layer on an input k13h_takes would accept apart
         from the k13h_slower list, unless its shape is in k13h_deep_slower."""
         return self.deep_projects and self._k13h_takes(x, ConvBiasAct.k13h_deep_slower)
+
+    def kernel_for(self, x):
+        """The 1x1 kernel that takes `x`, or None.  THE priority order of this class: 'k13h_deep', then 'k13h' (a
+        16-bit tensor; K13 and K20 read f32 alone), then 'k20', then 'k13' (an f32 tensor, which K13h refuses); None
+        is the library.  A new 1x1 kernel gets its place here."""
+        if x.dtype != torch.float32:
+            return 'k13h_deep' if self.k13h_deep_takes(x) else 'k13h' if self.k13h_takes(x) else None
+        if not self.k13_takes(x):
+            return None
+        return 'k20' if self._k20_for_k13(x) else 'k13'
+
+    def path(self, x, residual=None, pre=None, defer_epilogue=False):
+        """Which path forward(x, residual, pre=pre, defer_epilogue=defer_epilogue) runs, as last_path will say it: the
+        kernel_for(x) if its epilogue can add `residual` ('_gate' behind it where the squeeze-excite block in front
+        handed the gate of this very `x` over), 'library' otherwise.  `x` as it enters the convolution: the first
+        convolution of a 16-bit copy casts before it asks."""
+        kernel = None if defer_epilogue or not _addable(residual, x) else self.kernel_for(x)
+        if kernel is None:
+            return 'library'
+        held = self._gate if pre is None else None
+        return kernel if held is None or held[0] is not x else kernel + '_gate'
+
+    def applies_gate(self, x):
+        """To the squeeze-excite block in front: will forward(x) multiply `x` by the gate itself (give_gate), as a
+        1x1 kernel stages it?  (A skip that the kernel cannot add sends the call to the library path after all:
+        forward multiplies there.)"""
+        return self.kernel_for(x) is not None
 
     def give_gate(self, x, gate):
         """Hands over the squeeze-excite gate [B, C] f32 of `x`: the next forward(x) applies it."""
@@ -537,52 +606,36 @@ class ConvBiasAct(nn.Module):
 
     def forward(self, x, residual=None, defer_epilogue=False, pre=None):
         """defer_epilogue / pre: between the two layers of an armed FusedMBConv (FusedMBConv._forward_pre) only.
-        defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way,
-        and its "+ bias, activation" is applied here, inside K13: the block passes `pre` only after
-        k13_accepts(x, residual) said yes, and finishes x with K10 itself otherwise."""
+        defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way:
+        its "+ bias, activation" is applied here, inside K13 or K20 where one takes `x`, by K10 in front of the library
+        path otherwise."""
         if defer_epilogue:
             self.last_path = 'library'
             return self.conv(x)
-        if pre is not None:  # (the block asked k13_accepts(x, residual) for this very tensor)
-            from . import kernels
-            self._gate = None
-            if self.k20_takes(x):
-                self.last_path = 'k20'
-                return kernels.conv1x1_bias_act_split(x, self.weight_split(), self.bias, self.act_name,
-                                                      residual=residual, in_bias=pre.bias, in_act=pre.act_name)
-            self.last_path = 'k13'
-            return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, residual=residual,
-                                            in_bias=pre.bias, in_act=pre.act_name)
+        if pre is None:
+            x0, x = x, _to_copy_dtype(x, self.conv.weight)
+            if x is not x0 and self._gate is not None and self._gate[0] is x0:
+                self._gate = (x, self._gate[1])  # (a gate handed over for the tensor stays with its cast copy)
+        # (ConvBiasAct's own order: a subclass has asked for the kernel it puts in front, and of the tensor as it came)
+        path = self.last_path = ConvBiasAct.path(self, x, residual, pre)
         held, self._gate = self._gate, None
-        gate = held[1] if held is not None and held[0] is x else None
-        w16 = self.conv.weight.dtype
-        if x.dtype != w16 and w16 in (torch.float16, torch.bfloat16) and not torch.is_autocast_enabled(x.device.type):
-            x = x.to(w16)  # the first convolution of a 16-bit copy: the input is cast once, here
-        skip_ok = residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                       and residual.data_ptr() % 16 == 0)
-        if skip_ok and self.k13h_deep_takes(x):
-            from . import kernels
-            self.last_path = 'k13h_deep' if gate is None else 'k13h_deep_gate'
-            return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
-                                              residual=residual, config=ConvBiasAct.deep_config)
-        if skip_ok and self.k13h_takes(x):
-            from . import kernels
-            self.last_path = 'k13h' if gate is None else 'k13h_gate'
-            return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate,
-                                              residual=residual)
-        if self.k13_accepts(x, residual):
-            from . import kernels
-            if self.k20_takes(x):
-                self.last_path = 'k20' if gate is None else 'k20_gate'
+        gate = held[1] if pre is None and held is not None and held[0] is x else None
+        if path == 'library':
+            if pre is not None:
+                x = _finish_bias_act(pre, x, None)
+            if gate is not None:  # (the gate was handed over for a 1x1 kernel that cannot add this skip)
+                x = x * gate.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
+            return _library_conv_bias_act(self, x, residual)
+        kernel = path if gate is None else path[:-len('_gate')]
+        if kernel in ('k13', 'k20'):
+            pre_args = {} if pre is None else dict(in_bias=pre.bias, in_act=pre.act_name)
+            if kernel == 'k20':
                 return kernels.conv1x1_bias_act_split(x, self.weight_split(), self.bias, self.act_name, gate=gate,
-                                                      residual=residual)
-            self.last_path = 'k13' if gate is None else 'k13_gate'
+                                                      residual=residual, **pre_args)
             return kernels.conv1x1_bias_act(x, self.conv.weight, self.bias, self.act_name, gate=gate,
-                                            residual=residual)
-        self.last_path = 'library'
-        if gate is not None:  # (not reached when the gate was handed over: k13_takes(x) was checked)
-            x = x * gate.to(x.dtype).view(x.shape[0], x.shape[1], 1, 1)
-        return _library_conv_bias_act(self, x, residual)
+                                            residual=residual, **pre_args)
+        return kernels.conv1x1_bias_act16(x, self.conv.weight, self.bias, self.act_name, gate=gate, residual=residual,
+                                          config=ConvBiasAct.deep_config if kernel == 'k13h_deep' else 'auto')
 
 
 def _library_conv_bias_act(mod, x, residual):
@@ -596,10 +649,7 @@ def _finish_bias_act(mod, y, residual):
     # K10 moves 16 bytes per lane: planes of a multiple of the vector width (7x7 maps at 224 px,
     # 5x5 at 160 px are not), 16-byte aligned storage; everything else takes the torch ops
     hw_vec_ok = (y.shape[2] * y.shape[3]) % (16 // y.element_size()) == 0
-    if y.is_cuda and y.is_contiguous() and hw_vec_ok and y.data_ptr() % 16 == 0 and (
-            residual is None or (residual.dtype == y.dtype and residual.is_contiguous()
-                                 and residual.data_ptr() % 16 == 0)):
-        from . import kernels
+    if y.is_cuda and y.is_contiguous() and hw_vec_ok and y.data_ptr() % 16 == 0 and _addable(residual, y):
         if getattr(mod, 'emit_mean', False) and residual is None:
             y, mean = kernels.bias_act_rowmean_(y, mod.bias, mod.act_name)
             mod._mean = (y, mean)
@@ -627,7 +677,6 @@ class Conv3x3BiasAct(nn.Module):
     def __init__(self, conv, bias, act):
         super().__init__()
         self.conv = conv
-        from . import kernels
         self.register_buffer('weight_packed', kernels.pack_conv3x3_weight(conv.weight))  # [Cout, 3, 3, Cin]
         self.register_buffer('bias', bias.detach().float().contiguous())
         self.act = act
@@ -637,35 +686,30 @@ class Conv3x3BiasAct(nn.Module):
 
     @staticmethod
     def applies_to(conv):
-        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
-                and conv.dilation == (1, 1) and conv.stride in ((1, 1), (2, 2)) and conv.padding == (1, 1)
-                and conv.padding_mode == 'zeros' and conv.in_channels % 8 == 0)
+        return _dense_3x3(conv, strides=((1, 1), (2, 2))) and conv.in_channels % 8 == 0
 
     def k14h_takes(self, x):
         """Whether forward(x) runs on K14h: a CUDA NCHW-contiguous input of the copy's dtype, autocast off, no
         gradient wanted, a shape the C entry accepts and that is not listed as slower."""
         c = self.conv
         if not (Conv3x3BiasAct.use_k14h and x.is_cuda and x.dim() == 4 and x.dtype == c.weight.dtype
-                and x.dtype in (torch.float16, torch.bfloat16) and c.bias is None):
-            return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and c.weight.requires_grad):
+                and x.dtype in _16BIT and c.bias is None and _inference_call(c.weight)):
             return False
         if (c.in_channels, c.out_channels, self.stride, x.shape[2], x.shape[3]) in Conv3x3BiasAct.k14h_slower:
             return False
-        from . import kernels
         return kernels.conv3x3_16_supported(x, self.weight_packed, self.stride)
 
+    def path(self, x, residual=None):
+        """Which path forward(x, residual) runs, as last_path will say it: 'k14h', then 'library'.  `x` as it enters
+        the convolution (the first convolution of a 16-bit copy casts before it asks)."""
+        return 'k14h' if self.k14h_takes(x) and _addable(residual, x) else 'library'
+
     def forward(self, x, residual=None):
-        w16 = self.conv.weight.dtype
-        if x.dtype != w16 and w16 in (torch.float16, torch.bfloat16) and not torch.is_autocast_enabled(x.device.type):
-            x = x.to(w16)  # the first convolution of a 16-bit copy: the input is cast once, here
-        if self.k14h_takes(x) and (residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                                        and residual.data_ptr() % 16 == 0)):
-            from . import kernels
-            self.last_path = 'k14h'
+        x = _to_copy_dtype(x, self.conv.weight)
+        self.last_path = self.path(x, residual)
+        if self.last_path == 'k14h':
             return kernels.conv3x3_bias_act16(x, self.weight_packed, self.bias, self.act_name, self.stride,
                                               residual=residual)
-        self.last_path = 'library'
         return _library_conv_bias_act(self, x, residual)
 
 
@@ -684,30 +728,28 @@ class StemConvBiasAct(ConvBiasAct):
     k17_slower = frozenset()
 
     def __init__(self, conv, bias, act):
-        super().__init__(conv, bias, act)
+        super().__init__(conv, bias, act)  # (last_path: 'k17' or 'library')
         self._handed = None
-        self.last_path = None  # 'k17' or 'library': what the last forward ran (tests, A/B runs)
 
     @staticmethod
     def applies_to(conv):
-        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
-                and conv.dilation == (1, 1) and conv.stride == (2, 2) and conv.padding == (1, 1)
-                and conv.padding_mode == 'zeros' and conv.in_channels == 3)
+        return _dense_3x3(conv, strides=((2, 2),)) and conv.in_channels == 3
 
     def k17_takes(self, x):
         """Whether forward(x) runs on K17: a CUDA input, contiguous or channels_last, of the copy's dtype (or f32 in
         front of a 16-bit copy), autocast off, no gradient wanted, a shape the C entry accepts and that is not listed
         as slower."""
         c = self.conv
-        if not (StemConvBiasAct.use_k17 and x.is_cuda and x.dim() == 4 and c.bias is None and not self.emit_mean):
-            return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (c.weight.requires_grad
-                                                                               or x.requires_grad)):
+        if not (StemConvBiasAct.use_k17 and x.is_cuda and x.dim() == 4 and c.bias is None and not self.emit_mean
+                and _inference_call(c.weight, x=x)):
             return False
         if (c.out_channels, x.shape[2], x.shape[3]) in StemConvBiasAct.k17_slower:
             return False
-        from . import kernels
         return kernels.stem_conv_supported(x, c.weight)
+
+    def path(self, x, residual=None):
+        """'k17' in front of ConvBiasAct's order (which, for a 3x3 layer, says 'library')."""
+        return 'k17' if residual is None and self.k17_takes(x) else super().path(x, residual)
 
     def hand_over(self, x):
         """From the Preproc in front: `x` comes WITHOUT x * 2 - 1 applied; the next forward(x) applies it."""
@@ -716,8 +758,7 @@ class StemConvBiasAct(ConvBiasAct):
     def forward(self, x, residual=None):
         held, self._handed = self._handed, None
         raw = held is not None and held is x  # Preproc left x * 2 - 1 to this module
-        if residual is None and self.k17_takes(x):
-            from . import kernels
+        if self.path(x, residual) == 'k17':
             self.last_path = 'k17'
             return kernels.stem_conv_bias_act(x, self.conv.weight, self.bias, self.act_name, preproc=raw)
         if raw:  # (Preproc asked k17_takes(x) before it handed x over; whatever changed since: never un-preprocessed)
@@ -741,26 +782,17 @@ class WinogradConv3x3BiasAct(ConvBiasAct):
     k19_slower = frozenset({(512, 512, 8, 8)})
 
     def __init__(self, conv, bias, act):
-        super().__init__(conv, bias, act)
+        super().__init__(conv, bias, act)  # (last_path: 'k19' or 'library')
         self._wu = None
-        self.last_path = None  # 'k19' or 'library': what the last forward ran (tests, A/B runs)
 
     @staticmethod
     def applies_to(conv):
-        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.kernel_size == (3, 3)
-                and conv.dilation == (1, 1) and conv.stride == (1, 1) and conv.padding == (1, 1)
-                and conv.padding_mode == 'zeros' and conv.in_channels % 4 == 0)
+        return _dense_3x3(conv, strides=((1, 1),)) and conv.in_channels % 4 == 0
 
     def weight_u(self):
         """The conv's weight transformed for K19 ([16, Cout, Cin], kernels.pack_conv3x3_winograd_weight): made on the
-        first K19 forward and again whenever the weight has moved or been written since (not part of the state dict).
-        An inference tensor carries no version counter: a weight created under inference_mode and then written in
-        place keeps a stale U (as SqueezeExcite._fc2_wt); set self._wu = None after such a write."""
-        w = self.conv.weight
-        key = (w.data_ptr(), w.device, None if w.is_inference() else w._version)
-        if self._wu is None or self._wu[0] != key:
-            from . import kernels
-            self._wu = (key, kernels.pack_conv3x3_winograd_weight(w))
+        first K19 forward and kept as _derived_weight says."""
+        self._wu = _derived_weight(self._wu, self.conv.weight, kernels.pack_conv3x3_winograd_weight)
         return self._wu[1]
 
     def k19_takes(self, x):
@@ -769,23 +801,23 @@ class WinogradConv3x3BiasAct(ConvBiasAct):
         c = self.conv
         if not (WinogradConv3x3BiasAct.use_k19 and not self.emit_mean and x.is_cuda and x.dim() == 4
                 and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
-                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0):
-            return False
-        if torch.is_autocast_enabled('cuda') or (torch.is_grad_enabled() and (c.weight.requires_grad
-                                                                               or x.requires_grad)):
+                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
+                and _inference_call(c.weight, x=x)):
             return False
         B, K, H, W = x.shape
         if K != c.in_channels or (K, c.out_channels, H, W) in WinogradConv3x3BiasAct.k19_slower:
             return False
-        from . import _lib
         return _lib.load().mtr_conv3x3_winograd_lds_bytes(B, K, c.out_channels, H, W) > 0
 
+    def path(self, x, residual=None, pre=None, defer_epilogue=False):
+        """'k19' in front of ConvBiasAct's order (which, for a 3x3 layer, says 'library')."""
+        if not defer_epilogue and pre is None and self.k19_takes(x) and _addable(
+                residual, x, shape=(x.shape[0], self.conv.out_channels) + x.shape[2:]):
+            return 'k19'
+        return super().path(x, residual, pre, defer_epilogue)
+
     def forward(self, x, residual=None, defer_epilogue=False, pre=None):
-        if not defer_epilogue and pre is None and self.k19_takes(x) and (
-                residual is None or (residual.dtype == x.dtype and residual.is_contiguous()
-                                     and residual.shape == (x.shape[0], self.conv.out_channels) + x.shape[2:]
-                                     and residual.data_ptr() % 16 == 0)):
-            from . import kernels
+        if self.path(x, residual, pre, defer_epilogue) == 'k19':
             self.last_path = 'k19'
             return kernels.conv3x3_winograd_bias_act(x, self.weight_u(), self.bias, self.act_name, residual=residual)
         return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
@@ -839,44 +871,42 @@ class DepthwiseBiasAct(nn.Module):
     take_mean = ConvBiasAct.take_mean
     take_mean_f32 = ConvBiasAct.take_mean_f32
 
-    def _k18_takes(self, x, kernels):
+    def _k18_takes(self, x):
         """An armed layer's input (cuda, contiguous, f32 / f16 / bf16) goes to K18 instead of K11."""
         B, C, H, W = x.shape
-        return (DepthwiseBiasAct.use_k18 and not torch.is_autocast_enabled('cuda')
+        return (DepthwiseBiasAct.use_k18 and _autocast_off()
                 and self.stride == 1 and self.pads is None
                 and kernels.depthwise3x3_blocks_supported(x.dtype, H, W, self.stride, self.pad, x.data_ptr())
                 and not kernels.k11_takes_block_kernel(H, W) and 0 < B * C < 2 ** 24
                 and (C, H, W) not in DepthwiseBiasAct.k18_slower)
 
-    def forward(self, x):
+    def path(self, x):
+        """Which path forward(x) runs, as last_path will say it: 'k18' (an armed 3x3 layer), then 'k11' (3x3) or 'k15'
+        (5x5), then 'library' (the torch ops)."""
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
         ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
-        pad = self.pad if self.pads is None else self.pads
-        if x.is_cuda and x.is_contiguous() and ow % 4 == 0 and \
-                x.dtype in (torch.float32, torch.float16, torch.bfloat16):
-            from . import kernels
-            if self.k == 3 and self.block_depthwise and self._k18_takes(x, kernels):
-                self.last_path = 'k18'
-                if self.emit_mean:
-                    y, mean = kernels.depthwise3x3_blocks_bias_act(x, self.weight, self.bias, self.act_name,
-                                                                   want_mean=True)
-                    self._mean = (y, mean)
-                    return y
-                return kernels.depthwise3x3_blocks_bias_act(x, self.weight, self.bias, self.act_name)
-            if self.k == 3:
-                fn, self.last_path = kernels.depthwise3x3_bias_act, 'k11'
-            elif (x.shape[1], x.shape[2], x.shape[3], self.stride) not in DepthwiseBiasAct.k15_slower and \
-                    kernels.depthwise5x5_supported(x.shape[2], x.shape[3], pad):
-                fn, self.last_path = kernels.depthwise5x5_bias_act, 'k15'
+        if not (x.is_cuda and x.is_contiguous() and ow % 4 == 0 and x.dtype in _FLOATS):
+            return 'library'
+        if self.k == 3:
+            return 'k18' if self.block_depthwise and self._k18_takes(x) else 'k11'
+        if (x.shape[1], x.shape[2], x.shape[3], self.stride) not in DepthwiseBiasAct.k15_slower and \
+                kernels.depthwise5x5_supported(x.shape[2], x.shape[3], self.pad if self.pads is None else self.pads):
+            return 'k15'
+        return 'library'
+
+    def forward(self, x):
+        path = self.last_path = self.path(x)
+        if path != 'library':
+            if path == 'k18':
+                fn, geometry = kernels.depthwise3x3_blocks_bias_act, ()
             else:
-                fn = None
-            if fn is not None:
-                if self.emit_mean:
-                    y, mean = fn(x, self.weight, self.bias, self.act_name, self.stride, pad, want_mean=True)
-                    self._mean = (y, mean)
-                    return y
-                return fn(x, self.weight, self.bias, self.act_name, self.stride, pad)
-        self.last_path = 'library'
+                fn = kernels.depthwise3x3_bias_act if path == 'k11' else kernels.depthwise5x5_bias_act
+                geometry = (self.stride, self.pad if self.pads is None else self.pads)
+            if not self.emit_mean:
+                return fn(x, self.weight, self.bias, self.act_name, *geometry)
+            y, mean = fn(x, self.weight, self.bias, self.act_name, *geometry, want_mean=True)
+            self._mean = (y, mean)
+            return y
         if self.pads is not None:
             x = F.pad(x, self.pads)
         y = F.conv2d(x, self.weight.to(x.dtype), self.bias.to(x.dtype), self.stride,
@@ -899,97 +929,57 @@ def _block_plus_skip(block, x):
     return x + block(x)
 
 
-def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                   block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False):
-    """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
-    of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
-    function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
-    every activation less.  EfficientNetV2-S forward at the bench shape: 13.3 -> 11.8 ms in f32,
-    11.6 -> 10.2 ms under f16 autocast (tools/experiments/bn_backend_probe.py).  The original keeps
-    its checkpoint-compatible parameters; the copy has conv biases and no BatchNorm2d.
-    fused_epilogue=True additionally runs "+ bias, activation" behind each folded convolution as one
-    in-place HIP pass (ConvBiasAct) instead of PyTorch-ROCm's two elementwise kernels.
-    dtype=torch.float16 / torch.bfloat16 (needs fused_epilogue=True) returns a 16-bit inference copy: the batch
-    norms are folded in f32, then every convolution weight that runs as a GEMM or MIOpen convolution (1x1, dense
-    3x3, stem, ResNet convs) is cast to `dtype` once.  The folded biases, the depthwise 3x3 and 5x5 layers (K11,
-    K15) and the squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is cast
-    at the first convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h and its dense
-    3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8: Conv3x3BiasAct) on K14h.
-    On an f32 copy (no dtype) fused_epilogue=True also arms every FusedMBConv whose block is exactly a dense 3x3
-    ConvBiasAct and a 1x1 ConvBiasAct project without activation: the 3x3 layer's K10 pass is left out and applied by
-    the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with the bits of
-    the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict.
-    fuse_blocks=True (needs a 16-bit dtype; off by default) additionally arms every FusedMBConv whose block is
-    exactly a Conv3x3BiasAct expand and a ConvBiasAct project without activation: such a block runs as ONE launch
-    (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and the chain everywhere
-    else (block .last_path 'k16h' / 'chain'; an unarmed block reports None).  The module tree and the state_dict are
-    those of the copy without the option.
-    fuse_stem=True (needs fused_epilogue=True; any dtype; off by default; independent of fuse_blocks) makes the stem
-    -- the first dense 3x3 stride-2 padding-1 Cin = 3 ConvBiasAct -- a StemConvBiasAct, which runs Preproc, the
-    convolution and its epilogue as ONE launch (K17) where that kernel takes the input and the library chain
-    everywhere else, and arms the Preproc directly in front of it to hand its input over untouched.  The
-    state_dict keys are those of the copy without the option.
-    block_depthwise=True (needs fused_epilogue=True; any dtype; off by default; independent of the other options)
-    arms every 3x3, stride-1, padding-1 DepthwiseBiasAct without a folded ZeroPad2d: such a layer runs K18, the
-    register-block kernel, on the planes that kernel takes and K11's own block kernel refuses (24x24 and 12x12 of
-    EfficientNetV2 at 384 px, 128x128 and 64x64 of MobileNetV3 at 256 px), and K11 everywhere else.  K18 returns
-    the bits of K11's generic kernel for the output and the mean, so the armed copy's features are torch.equal to
-    the default copy's.  A plain attribute on the layers: no module, buffer or state_dict key is added.
-    deep_projects=True (needs a 16-bit dtype; off by default; independent of the other options) arms every 1x1,
-    stride-1, ungrouped ConvBiasAct without activation that has Cin >= 768 and Cout > 160 -- the deep project
-    convolutions of the MBConv tails: 15 layers of EfficientNetV2-S, 60 of EfficientNetV2-L, none of MobileNetV3 or
-    ResNet.  An armed layer runs K13h in its deep-K configuration (ConvBiasAct.deep_config, .last_path 'k13h_deep' /
-    'k13h_deep_gate') with the squeeze-excite gate and the skip folded in, wherever K13h takes the input -- the
-    shapes of ConvBiasAct.k13h_slower, which run cast + x * gate + rocBLAS + K10 by default, included -- unless the
-    shape is in ConvBiasAct.k13h_deep_slower; everything else takes today's branch.  The armed layers' results
-    differ from the library chain's by rounding (another summation order), and are the bits of K13h's other
-    configurations.  A plain attribute on the layers: no module, buffer or state_dict key is added.
-    winograd3x3=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype -- K14h serves the 16-bit copies; off by
-    default; independent of fuse_stem and block_depthwise) makes every dense 3x3, stride-1, padding-1, ungrouped
-    ConvBiasAct with Cin % 4 == 0 that emits no mean a WinogradConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L,
-    13 of ResNet-18, none of MobileNetV3.  Such a layer runs Winograd F(2x2, 3x3) on the f32 MFMA with "+ bias", the
-    activation and the block's skip in one launch (K19, .last_path 'k19') where that kernel takes the input and the
-    shape is not in WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed
-    FusedMBConv expand block runs K19 with its own epilogue and then the project as a plain K13 call -- a plain K20
-    call with split_gemm=True -- (block .last_path 'k19').  Results differ from the default copy's by rounding (both
-    are Winograd evaluations with different summation orders).  The state_dict keys are those of the copy without the option.
-    split_gemm=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype; off by default; independent of every other
-    option) arms every ConvBiasAct that is 1x1, stride 1, unpadded, ungrouped and emits no mean -- the expand, project
-    and head-side 1x1 layers: such a layer runs K20 (.last_path 'k20' / 'k20_gate'; an armed FusedMBConv block reports
-    'k20_pre') wherever K13 would take the input, unless the shape is in ConvBiasAct.k20_slower: the f32 product on the
-    bf16 matrix cores, from operands split into three bf16 pieces each and the six largest of the nine cross products,
-    with K13's prologue, gate, epilogue and skip.  f32-grade (it passes K13's fp64 bound) but not K13's bits.
-    Everything K20 refuses runs exactly today's branch.  A plain attribute on the layers: no module, buffer or
-    state_dict key is added; the split weight is derived state, cached per weight storage and version.
-    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm; 16-bit:
-    fuse_blocks, fuse_stem, block_depthwise, deep_projects): no two of them arm the same field of the same module, and
-    each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
-    section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
-    module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
-    hand_to are taken after the replacements (WinogradConv3x3BiasAct, Conv3x3BiasAct, StemConvBiasAct); mean_from and
-    gate_to before them, at layers no replacement touches in these networks (those that emit a mean; the 1x1 projects).
-    tests/test_backbone_option_combos_host.py checks every reference of every combination."""
-    import copy
+# ---- fold_batchnorm: the steps, in the order fold_batchnorm calls them
+
+def _adjacent_children(net):
+    """(sequential, name of a, a, b) for every two adjacent children a, b of the Sequentials of `net` that are no
+    ConvBNAct: where one layer is wired to the next."""
+    for seq in net.modules():
+        if isinstance(seq, nn.Sequential) and not isinstance(seq, ConvBNAct):
+            names = list(seq._modules)
+            for a, b in zip(names, names[1:]):
+                yield seq, a, seq._modules[a], seq._modules[b]
+
+
+def _only_layer(blk):
+    """The folded layer of a ConvBNAct whose other children are folded away (Identity), else None."""
+    if isinstance(blk, ConvBNAct) and all(isinstance(m, nn.Identity) for m in list(blk)[1:]):
+        return blk[0]
+    return None
+
+
+def _expand_and_project(m, expand_classes):
+    """(expand, project) of a FusedMBConv whose block is exactly a dense 3x3 layer of one of `expand_classes` and a
+    plain 1x1 ConvBiasAct project without activation, neither emitting a mean; None for every other module."""
+    if not isinstance(m, FusedMBConv) or list(m.block._modules) != ['0', '1']:
+        return None
+    expand, project = _only_layer(m.block._modules['0']), _only_layer(m.block._modules['1'])
+    if type(expand) in expand_classes and type(project) is ConvBiasAct \
+            and expand.conv.kernel_size == (3, 3) and expand.conv.groups == 1 \
+            and not getattr(expand, 'emit_mean', False) and project.act is None and not project.emit_mean \
+            and _plain_1x1(project.conv) and project.conv.in_channels == expand.conv.out_channels:
+        return expand, project
+    return None
+
+
+def _replace_conv_bias_act(folded, cls, first_only=False):
+    """Makes every ConvBiasAct (the first one alone: first_only) that emits no mean and whose conv cls.applies_to a
+    `cls` around the same conv, bias and activation: same parameters, same state_dict keys.  -> the ConvBNAct blocks."""
+    done = []
+    for m in folded.modules():
+        if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct and not m[0].emit_mean and cls.applies_to(m[0].conv):
+            m[0] = cls(m[0].conv, m[0].bias, m[0].act)
+            done.append(m)
+            if first_only:
+                break
+    return done
+
+
+def _fold_convs(folded, fused_epilogue):
+    """Every ConvBNAct: the batch norm folded into the convolution (w' = w * gamma / sqrt(var + eps), b' = beta -
+    mean * gamma / sqrt(var + eps)); with fused_epilogue the conv becomes a ConvBiasAct (K10), or a DepthwiseBiasAct
+    (K11, K15) where that class applies."""
     from torch.nn.utils.fusion import fuse_conv_bn_eval
-    if backbone.training:
-        raise ValueError('fold_batchnorm needs the running statistics of an eval-mode network')
-    if dtype not in (None, torch.float16, torch.bfloat16):
-        raise ValueError(f'fold_batchnorm: dtype must be None, torch.float16 or torch.bfloat16, got {dtype}')
-    if dtype is not None and not fused_epilogue:
-        raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
-    if fuse_blocks and dtype is None:
-        raise ValueError('fold_batchnorm: fuse_blocks=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
-    if fuse_stem and not fused_epilogue:
-        raise ValueError('fold_batchnorm: fuse_stem=True needs fused_epilogue=True')
-    if block_depthwise and not fused_epilogue:
-        raise ValueError('fold_batchnorm: block_depthwise=True needs fused_epilogue=True')
-    if deep_projects and dtype is None:
-        raise ValueError('fold_batchnorm: deep_projects=True needs a 16-bit copy (dtype=torch.float16 / torch.bfloat16)')
-    if winograd3x3 and (dtype is not None or not fused_epilogue):
-        raise ValueError('fold_batchnorm: winograd3x3=True needs fused_epilogue=True and an f32 copy (no dtype=)')
-    if split_gemm and (dtype is not None or not fused_epilogue):
-        raise ValueError('fold_batchnorm: split_gemm=True needs fused_epilogue=True and an f32 copy (no dtype=)')
-    folded = copy.deepcopy(backbone)
     for m in folded.modules():
         if isinstance(m, ConvBNAct) and isinstance(m[1], nn.BatchNorm2d):
             conv = fuse_conv_bn_eval(m[0], m[1])
@@ -1005,110 +995,202 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
             m[1] = nn.Identity()
     if any(isinstance(m, nn.BatchNorm2d) for m in folded.modules()):
         raise ValueError('a BatchNorm2d outside a ConvBNAct block cannot be folded here')
-    if fused_epilogue:  # ZeroPad2d -> depthwise 3x3 / 5x5: the padding becomes an argument of K11 / K15
-        for seq in folded.modules():
-            if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
-                continue
-            names = list(seq._modules)
-            for n_pad, n_conv in zip(names, names[1:]):
-                pad, blk = seq._modules[n_pad], seq._modules[n_conv]
-                if isinstance(pad, nn.ZeroPad2d) and isinstance(blk, ConvBNAct) and \
-                        isinstance(blk[0], DepthwiseBiasAct) and blk[0].pad == 0:
-                    l, r, t, b = (int(p) for p in pad.padding)
-                    lo, hi = blk[0].k // 2, blk[0].k // 2 + 1  # what the C entries take: 1 / 2 (3x3), 2 / 3 (5x5)
-                    if 0 <= l <= lo and 0 <= t <= lo and 0 <= r <= hi and 0 <= b <= hi:
-                        blk[0].pads = (l, r, t, b)
-                        seq._modules[n_pad] = nn.Identity()
-    if fused_epilogue:  # conv -> squeeze-excite: the epilogue pass also emits the channel means
-        for seq in folded.modules():
-            if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
-                continue
-            kids = list(seq)
-            for prev, nxt in zip(kids, kids[1:]):
-                if isinstance(nxt, SqueezeExcite) and isinstance(prev, ConvBNAct) and \
-                        isinstance(prev[0], (ConvBiasAct, DepthwiseBiasAct)) and \
-                        all(isinstance(m, nn.Identity) for m in list(prev)[1:]):
-                    prev[0].emit_mean = True
-                    nxt.mean_from = (prev[0],)
-        # squeeze-excite -> project conv: the gate multiplies the project conv's input inside K13
-        for seq in folded.modules():
-            if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
-                continue
-            kids = list(seq)
-            for prev, nxt in zip(kids, kids[1:]):
-                if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and \
-                        isinstance(nxt[0], ConvBiasAct):
-                    prev.gate_to = (nxt[0],)
-    if winograd3x3:  # dense 3x3 stride 1: Winograd on the f32 MFMA with the epilogue (K19)
-        for m in folded.modules():
-            if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct and not m[0].emit_mean \
-                    and WinogradConv3x3BiasAct.applies_to(m[0].conv):
-                m[0] = WinogradConv3x3BiasAct(m[0].conv, m[0].bias, m[0].act)
-    if fused_epilogue and dtype is None:  # dense 3x3 -> project 1x1 of a FusedMBConv: the 3x3's epilogue inside K13
-        for m in folded.modules():
-            if isinstance(m, FusedMBConv) and list(m.block._modules) == ['0', '1']:
-                first, last = m.block._modules['0'], m.block._modules['1']
-                if isinstance(first, ConvBNAct) and isinstance(last, ConvBNAct) \
-                        and type(first[0]) in (ConvBiasAct, WinogradConv3x3BiasAct) \
-                        and type(last[0]) is ConvBiasAct \
-                        and all(isinstance(k, nn.Identity) for k in list(first)[1:] + list(last)[1:]) \
-                        and first[0].conv.kernel_size == (3, 3) and first[0].conv.groups == 1 \
-                        and not first[0].emit_mean and last[0].act is None and not last[0].emit_mean \
-                        and last[0].conv.kernel_size == (1, 1) and last[0].conv.stride == (1, 1) \
-                        and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
-                        and last[0].conv.in_channels == first[0].conv.out_channels:
-                    m.pre_pair = (first[0], last[0])
-    if dtype is not None:  # the 16-bit copy: GEMM / MIOpen weights cast once, not by autocast on every forward
-        for m in folded.modules():
-            if isinstance(m, ConvBiasAct):
-                m.conv.to(dtype)
-        for m in folded.modules():  # the dense 3x3 layers: K14h, on the weight repacked once
-            if isinstance(m, ConvBNAct) and isinstance(m[0], ConvBiasAct) and not m[0].emit_mean \
-                    and Conv3x3BiasAct.applies_to(m[0].conv):
-                m[0] = Conv3x3BiasAct(m[0].conv, m[0].bias, m[0].act)
-        folded.inference_dtype = dtype
-    if fuse_blocks:  # expand 3x3 -> project 1x1 of a FusedMBConv: one launch (K16h)
-        for m in folded.modules():
-            if isinstance(m, FusedMBConv) and list(m.block._modules) == ['0', '1']:
-                first, last = m.block._modules['0'], m.block._modules['1']
-                if isinstance(first, ConvBNAct) and isinstance(last, ConvBNAct) \
-                        and isinstance(first[0], Conv3x3BiasAct) and isinstance(last[0], ConvBiasAct) \
-                        and all(isinstance(k, nn.Identity) for k in list(first)[1:] + list(last)[1:]) \
-                        and last[0].act is None and not last[0].emit_mean \
-                        and last[0].conv.kernel_size == (1, 1) and last[0].conv.stride == (1, 1) \
-                        and last[0].conv.padding == (0, 0) and last[0].conv.groups == 1 \
-                        and last[0].conv.in_channels == first[0].conv.out_channels:
-                    m.fused_pair = (first[0], last[0])
-    if block_depthwise:  # depthwise 3x3 stride 1 padding 1: K18 where K11 would take its generic kernel
-        for m in folded.modules():
-            if isinstance(m, DepthwiseBiasAct) and m.k == 3 and m.stride == 1 and m.pad == 1 and m.pads is None:
-                m.block_depthwise = True
-    if deep_projects:  # the deep project convolutions: K13h's deep-K configuration, the listed-slower shapes included
-        for m in folded.modules():
-            c = m.conv if type(m) is ConvBiasAct else None
-            if c is not None and m.act is None and c.kernel_size == (1, 1) and c.stride == (1, 1) \
-                    and c.padding == (0, 0) and c.groups == 1 and c.in_channels >= 768 and c.out_channels > 160:
-                m.deep_projects = True
-    if split_gemm:  # 1x1 stride 1: the f32 product on the bf16 matrix cores from split operands (K20)
-        for m in folded.modules():
-            c = m.conv if isinstance(m, ConvBiasAct) else None
-            if c is not None and not m.emit_mean and c.kernel_size == (1, 1) and c.stride == (1, 1) \
-                    and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1:
-                m.split_gemm = True
-    if fuse_stem:  # Preproc -> stem 3x3 stride 2: one launch (K17)
-        stem_blk = next((m for m in folded.modules() if isinstance(m, ConvBNAct) and type(m[0]) is ConvBiasAct
-                         and not m[0].emit_mean and StemConvBiasAct.applies_to(m[0].conv)), None)
-        if stem_blk is not None:
-            stem_blk[0] = StemConvBiasAct(stem_blk[0].conv, stem_blk[0].bias, stem_blk[0].act)
-            for seq in folded.modules():
-                if not isinstance(seq, nn.Sequential) or isinstance(seq, ConvBNAct):
-                    continue
-                kids = list(seq)
-                for prev, nxt in zip(kids, kids[1:]):
-                    while isinstance(nxt, nn.Sequential) and not isinstance(nxt, ConvBNAct) and len(nxt):
-                        nxt = nxt[0]  # (EfficientNetV2: Preproc stands in front of the `features` container)
-                    if isinstance(prev, Preproc) and nxt is stem_blk:
-                        prev.hand_to = (stem_blk[0],)
+
+
+def _fold_paddings(folded):
+    """ZeroPad2d -> depthwise 3x3 / 5x5: the padding becomes an argument of K11 / K15."""
+    for seq, n_pad, pad, blk in _adjacent_children(folded):
+        if isinstance(pad, nn.ZeroPad2d) and isinstance(blk, ConvBNAct) and \
+                isinstance(blk[0], DepthwiseBiasAct) and blk[0].pad == 0:
+            l, r, t, b = (int(p) for p in pad.padding)
+            lo, hi = blk[0].k // 2, blk[0].k // 2 + 1  # what the C entries take: 1 / 2 (3x3), 2 / 3 (5x5)
+            if 0 <= l <= lo and 0 <= t <= lo and 0 <= r <= hi and 0 <= b <= hi:
+                blk[0].pads = (l, r, t, b)
+                seq._modules[n_pad] = nn.Identity()
+
+
+def _wire_squeeze_excite(folded):
+    """conv -> squeeze-excite: the epilogue pass in front also emits the channel means (mean_from, emit_mean).
+    squeeze-excite -> project conv: the gate multiplies the project conv's input inside its 1x1 kernel (gate_to)."""
+    for _, _, prev, nxt in _adjacent_children(folded):
+        if isinstance(nxt, SqueezeExcite) and isinstance(_only_layer(prev), (ConvBiasAct, DepthwiseBiasAct)):
+            prev[0].emit_mean = True
+            nxt.mean_from = (prev[0],)
+        if isinstance(prev, SqueezeExcite) and isinstance(nxt, ConvBNAct) and isinstance(nxt[0], ConvBiasAct):
+            prev.gate_to = (nxt[0],)
+
+
+def _replace_winograd(folded):
+    """winograd3x3: every dense 3x3, stride-1, padding-1, ungrouped ConvBiasAct with Cin % 4 == 0 that emits no mean
+    becomes a WinogradConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L, 13 of ResNet-18, none of MobileNetV3.
+    Such a layer runs Winograd F(2x2, 3x3) on the f32 MFMA with "+ bias", the activation and the block's skip in one
+    launch (K19, .last_path 'k19') where that kernel takes the input and the shape is not in
+    WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed FusedMBConv expand
+    block runs K19 with its own epilogue and then the project as a plain K13 call -- a plain K20 call with
+    split_gemm=True -- (block .last_path 'k19').  Results differ from the default copy's by rounding (both are Winograd
+    evaluations with different summation orders)."""
+    _replace_conv_bias_act(folded, WinogradConv3x3BiasAct)
+
+
+def _arm_pre_pairs(folded):
+    """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the WinogradConv3x3BiasAct
+    that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
+    and applied by the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with
+    the bits of the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict."""
+    for m in folded.modules():
+        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct))
+        if pair:
+            m.pre_pair = pair
+
+
+def _cast_16bit(folded, dtype):
+    """The 16-bit copy: every convolution weight that runs as a GEMM or MIOpen convolution (1x1, dense 3x3, stem,
+    ResNet convs) is cast to `dtype` once, not by autocast on every forward.  The folded biases, the depthwise layers
+    (K11, K15) and the squeeze-excite blocks (K12) keep f32 parameters.  The copy computes in `dtype` (its input is
+    cast at the first convolution; run it with autocast off), its 1x1 stride-1 convolutions run on K13h, and its dense
+    3x3 convolutions (stride 1 or 2, padding 1, Cin a multiple of 8) become Conv3x3BiasAct: K14h, on the weight
+    repacked once."""
+    for m in folded.modules():
+        if isinstance(m, ConvBiasAct):
+            m.conv.to(dtype)
+    _replace_conv_bias_act(folded, Conv3x3BiasAct)
+    folded.inference_dtype = dtype
+
+
+def _arm_fused_pairs(folded):
+    """fuse_blocks: every FusedMBConv whose block is exactly a Conv3x3BiasAct expand and a ConvBiasAct project without
+    activation runs as ONE launch (K16h) where that kernel takes the input, with the bits of the two-kernel chain, and
+    the chain everywhere else (block .last_path 'k16h' / 'chain'; an unarmed block reports None)."""
+    for m in folded.modules():
+        pair = _expand_and_project(m, (Conv3x3BiasAct,))
+        if pair:
+            m.fused_pair = pair
+
+
+def _arm_block_depthwise(folded):
+    """block_depthwise: every 3x3, stride-1, padding-1 DepthwiseBiasAct without a folded ZeroPad2d runs K18, the
+    register-block kernel, on the planes that kernel takes and K11's own block kernel refuses (24x24 and 12x12 of
+    EfficientNetV2 at 384 px, 128x128 and 64x64 of MobileNetV3 at 256 px), and K11 everywhere else.  K18 returns the
+    bits of K11's generic kernel for the output and the mean, so the armed copy's features are torch.equal to the
+    default copy's."""
+    for m in folded.modules():
+        if isinstance(m, DepthwiseBiasAct) and m.k == 3 and m.stride == 1 and m.pad == 1 and m.pads is None:
+            m.block_depthwise = True
+
+
+def _arm_deep_projects(folded):
+    """deep_projects: every plain 1x1 ConvBiasAct without activation that has Cin >= 768 and Cout > 160 -- the deep
+    project convolutions of the MBConv tails: 15 layers of EfficientNetV2-S, 60 of EfficientNetV2-L, none of
+    MobileNetV3 or ResNet.  An armed layer runs K13h in its deep-K configuration (ConvBiasAct.deep_config, .last_path
+    'k13h_deep' / 'k13h_deep_gate') with the squeeze-excite gate and the skip folded in, wherever K13h takes the input
+    -- the shapes of ConvBiasAct.k13h_slower, which run cast + x * gate + rocBLAS + K10 by default, included -- unless
+    the shape is in ConvBiasAct.k13h_deep_slower; everything else takes today's branch.  The armed layers' results
+    differ from the library chain's by rounding (another summation order), and are the bits of K13h's other
+    configurations."""
+    for m in folded.modules():
+        if type(m) is ConvBiasAct and m.act is None and _plain_1x1(m.conv) and m.conv.in_channels >= 768 \
+                and m.conv.out_channels > 160:
+            m.deep_projects = True
+
+
+def _arm_split_gemm(folded):
+    """split_gemm: every plain 1x1 ConvBiasAct that emits no mean -- the expand, project and head-side 1x1 layers --
+    runs K20 (.last_path 'k20' / 'k20_gate'; an armed FusedMBConv block reports 'k20_pre') wherever K13 would take the
+    input, unless the shape is in ConvBiasAct.k20_slower: the f32 product on the bf16 matrix cores, from operands split
+    into three bf16 pieces each and the six largest of the nine cross products, with K13's prologue, gate, epilogue and
+    skip.  f32-grade (it passes K13's fp64 bound) but not K13's bits.  Everything K20 refuses runs exactly today's
+    branch.  The split weight is derived state, cached per weight storage and version."""
+    for m in folded.modules():
+        if isinstance(m, ConvBiasAct) and not m.emit_mean and _plain_1x1(m.conv):
+            m.split_gemm = True
+
+
+def _fuse_stem(folded):
+    """fuse_stem: the stem -- the first dense 3x3 stride-2 padding-1 Cin = 3 ConvBiasAct -- becomes a StemConvBiasAct,
+    which runs Preproc, the convolution and its epilogue as ONE launch (K17) where that kernel takes the input and the
+    library chain everywhere else; the Preproc directly in front of it is armed to hand its input over untouched."""
+    for stem_blk in _replace_conv_bias_act(folded, StemConvBiasAct, first_only=True):
+        for _, _, prev, nxt in _adjacent_children(folded):
+            while isinstance(nxt, nn.Sequential) and not isinstance(nxt, ConvBNAct) and len(nxt):
+                nxt = nxt[0]  # (EfficientNetV2: Preproc stands in front of the `features` container)
+            if isinstance(prev, Preproc) and nxt is stem_blk:
+                prev.hand_to = (stem_blk[0],)
+
+
+# what an option needs of (fused_epilogue, dtype), and how the error says it
+_NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
+          '16bit': (lambda fused, dtype: dtype is not None, 'a 16-bit copy (dtype=torch.float16 / torch.bfloat16)'),
+          'f32': (lambda fused, dtype: fused and dtype is None, 'fused_epilogue=True and an f32 copy (no dtype=)')}
+_OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
+                 ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'))
+
+
+def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
+                   block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False):
+    """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
+    of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
+    function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
+    every activation less.  EfficientNetV2-S forward at the bench shape: 13.3 -> 11.8 ms in f32,
+    11.6 -> 10.2 ms under f16 autocast (tools/experiments/bn_backend_probe.py).  The original keeps
+    its checkpoint-compatible parameters; the copy has conv biases and no BatchNorm2d.
+    fused_epilogue=True additionally runs "+ bias, activation" behind each folded convolution as one
+    in-place HIP pass (ConvBiasAct) instead of PyTorch-ROCm's two elementwise kernels, folds the explicit paddings into
+    the depthwise kernels (_fold_paddings), wires the squeeze-excite blocks to the layers around them
+    (_wire_squeeze_excite) and, on an f32 copy, arms the FusedMBConv blocks for the K13 prologue (_arm_pre_pairs).
+    dtype=torch.float16 / torch.bfloat16 (needs fused_epilogue=True) returns a 16-bit inference copy (_cast_16bit).
+    The options, all off by default; each step's docstring says what it arms.  None adds a module, a buffer or a
+    state_dict key to the copy without it:
+    fuse_blocks=True (needs a 16-bit dtype): FusedMBConv blocks as one launch, K16h (_arm_fused_pairs).
+    fuse_stem=True (needs fused_epilogue=True; any dtype): Preproc and the stem as one launch, K17 (_fuse_stem).
+    block_depthwise=True (needs fused_epilogue=True; any dtype): K18 where K11 would take its generic kernel
+    (_arm_block_depthwise).
+    deep_projects=True (needs a 16-bit dtype): the deep project convolutions on K13h's deep-K configuration
+    (_arm_deep_projects).
+    winograd3x3=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype -- K14h serves the 16-bit copies): the
+    dense 3x3 stride-1 layers as Winograd on the f32 MFMA, K19 (_replace_winograd).
+    split_gemm=True (needs fused_epilogue=True and an f32 copy): the f32 1x1 layers on K20 (_arm_split_gemm).
+    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm; 16-bit:
+    fuse_blocks, fuse_stem, block_depthwise, deep_projects): no two of them arm the same field of the same module, and
+    each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
+    section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
+    module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
+    hand_to are taken after the replacements (WinogradConv3x3BiasAct, Conv3x3BiasAct, StemConvBiasAct); mean_from and
+    gate_to before them, at layers no replacement touches in these networks (those that emit a mean; the 1x1 projects).
+    tests/test_backbone_option_combos_host.py checks every reference of every combination."""
+    import copy
+    if backbone.training:
+        raise ValueError('fold_batchnorm needs the running statistics of an eval-mode network')
+    if dtype not in (None,) + _16BIT:
+        raise ValueError(f'fold_batchnorm: dtype must be None, torch.float16 or torch.bfloat16, got {dtype}')
+    if dtype is not None and not fused_epilogue:
+        raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
+    options = dict(fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
+                   deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm)
+    for option, need in _OPTION_NEEDS:
+        met, text = _NEEDS[need]
+        if options[option] and not met(fused_epilogue, dtype):
+            raise ValueError(f'fold_batchnorm: {option}=True needs {text}')
+    folded = copy.deepcopy(backbone)
+    _fold_convs(folded, fused_epilogue)
+    if fused_epilogue:
+        _fold_paddings(folded)
+        _wire_squeeze_excite(folded)
+    if winograd3x3:
+        _replace_winograd(folded)
+    if fused_epilogue and dtype is None:
+        _arm_pre_pairs(folded)
+    if dtype is not None:
+        _cast_16bit(folded, dtype)
+    if fuse_blocks:
+        _arm_fused_pairs(folded)
+    if block_depthwise:
+        _arm_block_depthwise(folded)
+    if deep_projects:
+        _arm_deep_projects(folded)
+    if split_gemm:
+        _arm_split_gemm(folded)
+    if fuse_stem:
+        _fuse_stem(folded)
     return folded
 
 

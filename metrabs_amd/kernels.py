@@ -749,6 +749,15 @@ def se_gate(mean, w1, b1, w2, b2, act, gate_fn, out=None, w2t=None, config=-1):
     return out
 
 
+def _residual_and_out(fn, x, shape, residual, out, hw='H, W'):
+    """What the convolution wrappers below ask of a skip connection and of a caller's `out`: `shape` (the output's),
+    x's dtype, contiguous.  -> `out`, allocated here when None.  `fn` and `hw` go into the error text."""
+    for name, t in (('residual', residual), ('out', out)):
+        if t is not None and (t.shape != shape or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError(f'{fn}: {name} must be [B, Cout, {hw}] like the output, contiguous')
+    return torch.empty(shape, device=x.device, dtype=x.dtype) if out is None else out
+
+
 # K13: 1x1 convolution as one f32 MFMA GEMM with the K10 epilogue (csrc/conv1x1.hip)
 
 def conv1x1_supported(x, weight):
@@ -798,13 +807,7 @@ def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config
         raise ValueError('conv1x1_bias_act: in_act needs in_bias')
     if in_bias is not None and (in_bias.dtype != torch.float32 or in_bias.numel() != K):
         raise ValueError('conv1x1_bias_act: in_bias must be [Cin] f32')
-    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
-                                 or not residual.is_contiguous()):
-        raise ValueError('conv1x1_bias_act: residual must be [B, Cout, H, W] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('conv1x1_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
+    out = _residual_and_out('conv1x1_bias_act', x, (B, M, H, W), residual, out)
     check(_lib.load().mtr_conv1x1_bias_act_pre(
         _ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
         None if in_bias is None else _ptr(in_bias.contiguous()), ACT_CODES[in_act],
@@ -860,13 +863,7 @@ def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None, conf
         raise ValueError(f'conv1x1_bias_act16: weight is {w.dtype}, x is {x.dtype}')
     if gate is not None and (gate.dtype != torch.float32 or gate.numel() != B * K):
         raise ValueError('conv1x1_bias_act16: gate must be [B, Cin] f32')
-    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
-                                 or not residual.is_contiguous()):
-        raise ValueError('conv1x1_bias_act16: residual must be [B, Cout, H, W] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('conv1x1_bias_act16: out must be [B, Cout, H, W] like the output, contiguous')
+    out = _residual_and_out('conv1x1_bias_act16', x, (B, M, H, W), residual, out)
     args = (_ptr(x), dtype_code(x.dtype), _ptr(w.contiguous()), _ptr(bias.contiguous().float()),
             None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
             ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device))
@@ -921,13 +918,7 @@ def conv3x3_bias_act16(x, w_packed, bias, act, stride, residual=None, out=None):
     if bias.numel() != M:
         raise ValueError(f'conv3x3_bias_act16: bias has {bias.numel()} elements, expected {M}')
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if residual is not None and (residual.shape != (B, M, Ho, Wo) or residual.dtype != x.dtype
-                                 or not residual.is_contiguous()):
-        raise ValueError('conv3x3_bias_act16: residual must be [B, Cout, Ho, Wo] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, Ho, Wo, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, Ho, Wo) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('conv3x3_bias_act16: out must be [B, Cout, Ho, Wo] like the output, contiguous')
+    out = _residual_and_out('conv3x3_bias_act16', x, (B, M, Ho, Wo), residual, out, hw='Ho, Wo')
     check(_lib.load().mtr_conv3x3_bias_act16(
         _ptr(x), dtype_code(x.dtype), _ptr(w_packed), _ptr(bias.contiguous().float()),
         None if residual is None else _ptr(residual), ACT_CODES[act], B, K, M, H, W, int(stride), _ptr(out),
@@ -984,15 +975,9 @@ def fused_mbconv16(x, w3_packed, bias3, act, stride, w1, bias1, residual=None, o
         raise ValueError(f'fused_mbconv16: biases have {bias3.numel()} and {bias1.numel()} elements, expected '
                          f'{Cmid} and {M}')
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if residual is not None:
-        if stride != 1 or M != K:
-            raise ValueError('fused_mbconv16: a residual needs stride 1 and Cout == Cin')
-        if residual.shape != (B, M, Ho, Wo) or residual.dtype != x.dtype or not residual.is_contiguous():
-            raise ValueError('fused_mbconv16: residual must be [B, Cout, Ho, Wo] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, Ho, Wo, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, Ho, Wo) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('fused_mbconv16: out must be [B, Cout, Ho, Wo] like the output, contiguous')
+    if residual is not None and (stride != 1 or M != K):
+        raise ValueError('fused_mbconv16: a residual needs stride 1 and Cout == Cin')
+    out = _residual_and_out('fused_mbconv16', x, (B, M, Ho, Wo), residual, out, hw='Ho, Wo')
     check(_lib.load().mtr_fused_mbconv16(
         _ptr(x), dtype_code(x.dtype), _ptr(w3_packed), _ptr(bias3.contiguous().float()), ACT_CODES[act],
         _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), None if residual is None else _ptr(residual),
@@ -1117,13 +1102,7 @@ def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
     M = w_u.shape[1]
     if bias.numel() != M:
         raise ValueError(f'conv3x3_winograd_bias_act: bias has {bias.numel()} elements, expected {M}')
-    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
-                                 or not residual.is_contiguous()):
-        raise ValueError('conv3x3_winograd_bias_act: residual must be [B, Cout, H, W] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('conv3x3_winograd_bias_act: out must be [B, Cout, H, W] like the output, contiguous')
+    out = _residual_and_out('conv3x3_winograd_bias_act', x, (B, M, H, W), residual, out)
     for t, name in ((x, 'x'), (residual, 'residual')):
         if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
                 and out.data_ptr() < t.data_ptr() + t.numel() * 4:
@@ -1200,13 +1179,7 @@ def conv1x1_bias_act_split(x, w_split, bias, act, gate=None, residual=None, in_b
         raise ValueError('conv1x1_bias_act_split: in_act needs in_bias')
     if in_bias is not None and (in_bias.dtype != torch.float32 or in_bias.numel() != K):
         raise ValueError('conv1x1_bias_act_split: in_bias must be [Cin] f32')
-    if residual is not None and (residual.shape != (B, M, H, W) or residual.dtype != x.dtype
-                                 or not residual.is_contiguous()):
-        raise ValueError('conv1x1_bias_act_split: residual must be [B, Cout, H, W] like the output, contiguous')
-    if out is None:
-        out = torch.empty(B, M, H, W, device=x.device, dtype=x.dtype)
-    elif out.shape != (B, M, H, W) or out.dtype != x.dtype or not out.is_contiguous():
-        raise ValueError('conv1x1_bias_act_split: out must be [B, Cout, H, W] like the output, contiguous')
+    out = _residual_and_out('conv1x1_bias_act_split', x, (B, M, H, W), residual, out)
     check(_lib.load().mtr_conv1x1_bias_act_split(
         _ptr(x), _ptr(w_split), _ptr(bias.contiguous().float()),
         None if in_bias is None else _ptr(in_bias.contiguous()), ACT_CODES[in_act],
