@@ -91,15 +91,12 @@ static int launch_bias_act_rowmean(void* y, const float* bias, float* row_mean, 
   const dim3 grid((unsigned)blocks), block(256);
   const float inv = 1.0f / (float)HW;
   MTR_CLEAR_STALE();
-  switch (act) {
-    case kActNone: hipLaunchKernelGGL((bias_act_rowmean_kernel<T, kActNone, LPR>), grid, block, 0, stream, (T*)y, bias, row_mean, n_rows, C, HW / VEC, inv); break;
-    case kActRelu: hipLaunchKernelGGL((bias_act_rowmean_kernel<T, kActRelu, LPR>), grid, block, 0, stream, (T*)y, bias, row_mean, n_rows, C, HW / VEC, inv); break;
-    case kActSilu: hipLaunchKernelGGL((bias_act_rowmean_kernel<T, kActSilu, LPR>), grid, block, 0, stream, (T*)y, bias, row_mean, n_rows, C, HW / VEC, inv); break;
-    case kActHardswish: hipLaunchKernelGGL((bias_act_rowmean_kernel<T, kActHardswish, LPR>), grid, block, 0, stream, (T*)y, bias, row_mean, n_rows, C, HW / VEC, inv); break;
-    default: return MTR_E_PARAM;
-  }
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return dispatch_act(act, [&](auto tag) -> int {
+    hipLaunchKernelGGL((bias_act_rowmean_kernel<T, decltype(tag)::value, LPR>), grid, block, 0, stream, (T*)y, bias,
+                       row_mean, n_rows, C, HW / VEC, inv);
+    MTR_CHECK_LAUNCH();
+    return MTR_OK;
+  });
 }
 
 template <typename T>
@@ -123,23 +120,17 @@ static int launch_bias_act(void* y, const float* bias, const void* residual, int
   const bool wide = n_vec > 0xffffffffLL;
   const FastDiv by_hw = make_fastdiv((unsigned)(HW / VEC)), by_c = make_fastdiv((unsigned)C);
   MTR_CLEAR_STALE();
-#define MTR_BIAS_ACT_LAUNCH(ACT)                                                                                 \
-  if (wide)                                                                                                      \
-    hipLaunchKernelGGL((bias_act_kernel<T, ACT, RES, true>), grid, block, 0, stream, (T*)y, bias,                \
-                       (const T*)residual, n_vec, C, HW / VEC, by_hw, by_c);                                    \
-  else                                                                                                           \
-    hipLaunchKernelGGL((bias_act_kernel<T, ACT, RES, false>), grid, block, 0, stream, (T*)y, bias,               \
-                       (const T*)residual, n_vec, C, HW / VEC, by_hw, by_c);
-  switch (act) {
-    case kActNone: MTR_BIAS_ACT_LAUNCH(kActNone) break;
-    case kActRelu: MTR_BIAS_ACT_LAUNCH(kActRelu) break;
-    case kActSilu: MTR_BIAS_ACT_LAUNCH(kActSilu) break;
-    case kActHardswish: MTR_BIAS_ACT_LAUNCH(kActHardswish) break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_BIAS_ACT_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return dispatch_act(act, [&](auto tag) -> int {
+    constexpr int ACT = decltype(tag)::value;
+    if (wide)
+      hipLaunchKernelGGL((bias_act_kernel<T, ACT, RES, true>), grid, block, 0, stream, (T*)y, bias,
+                         (const T*)residual, n_vec, C, HW / VEC, by_hw, by_c);
+    else
+      hipLaunchKernelGGL((bias_act_kernel<T, ACT, RES, false>), grid, block, 0, stream, (T*)y, bias,
+                         (const T*)residual, n_vec, C, HW / VEC, by_hw, by_c);
+    MTR_CHECK_LAUNCH();
+    return MTR_OK;
+  });
 }
 
 }  // namespace mtr

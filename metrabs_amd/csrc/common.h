@@ -73,6 +73,37 @@ __device__ __forceinline__ float activate(float x) {
   return x;
 }
 
+// An activation code as a type: what the dispatchers below hand to a generic lambda (decltype(tag)::value).
+template <int V> struct ActTag { static constexpr int value = V; };
+
+// Host: the run-time `act` code -> f(ActTag<code>{}), f's int returned; an unknown code is MTR_E_PARAM, f not called.
+template <typename F>
+inline int dispatch_act(int act, F&& f) {
+  switch (act) {
+    case kActNone: return f(ActTag<kActNone>{});
+    case kActRelu: return f(ActTag<kActRelu>{});
+    case kActSilu: return f(ActTag<kActSilu>{});
+    case kActHardswish: return f(ActTag<kActHardswish>{});
+    default: return MTR_E_PARAM;
+  }
+}
+// Host: the input prologue of the 1x1 kernels (their template parameter PRE): tag -1 without an in_bias, else in_act
+template <typename F>
+inline int dispatch_pre(const float* in_bias, int in_act, F&& f) {
+  return in_bias ? dispatch_act(in_act, f) : f(ActTag<-1>{});
+}
+// Device: the wave-uniform run-time code of a kernel that shares its main loop between the activations.  Every entry
+// point refuses an unknown code on the host, so the default is kActNone and nothing else.
+template <typename F>
+__device__ __forceinline__ void with_act(int act, F&& f) {
+  switch (act) {
+    case kActRelu: f(ActTag<kActRelu>()); break;
+    case kActSilu: f(ActTag<kActSilu>()); break;
+    case kActHardswish: f(ActTag<kActHardswish>()); break;
+    default: f(ActTag<kActNone>()); break;
+  }
+}
+
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(__half v) { return __half2float(v); }
 __device__ __forceinline__ float to_f32(__hip_bfloat16 v) { return __bfloat162float(v); }
@@ -88,6 +119,42 @@ __device__ __forceinline__ float to_f32(__hip_bfloat16 v) { return __bfloat162fl
 __device__ __forceinline__ float settled(float a) {
   asm("" : "+v"(a));
   return a;
+}
+
+// The input prologue of the 1x1 kernels (K13, K20; PRE -1: none): K10's epilogue of the convolution in front, left out
+// there and applied to every staged element here -- K10's expression, the f32 value K10 would have stored.
+template <int PRE>
+__device__ __forceinline__ float input_prologue(float v, float bi) {
+  if constexpr (PRE >= 0) return settled(activate<PRE>(v + bi));
+  return v;
+}
+
+// The epilogue of the f32 1x1 kernels (K13, K20): four consecutive positions of one output channel, at element `off`
+// of y -- K10's "+ bias", activation, "+ skip" in registers, one 16-byte store.
+template <int ACT>
+__device__ __forceinline__ void epilogue_store4(float a0, float a1, float a2, float a3, float bm,
+                                                const float* __restrict__ residual, float* __restrict__ y,
+                                                long long off) {
+  float4 r;
+  r.x = activate<ACT>(a0 + bm);
+  r.y = activate<ACT>(a1 + bm);
+  r.z = activate<ACT>(a2 + bm);
+  r.w = activate<ACT>(a3 + bm);
+  if (residual) {  // the block's skip connection, added after the activation (K10's order)
+    const float4 q = *reinterpret_cast<const float4*>(residual + off);
+    r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+  }
+  *reinterpret_cast<float4*>(y + off) = r;
+}
+
+// Positive sizes, whole 16-byte groups (`group` elements: 4 of f32, 8 of 16 bits) of positions and of k, and every
+// index a kernel forms in 32 bits: what the 1x1 entry points (K13, K13h, K20) refuse as MTR_E_SHAPE.
+inline int conv1x1_shape_check(long long B, int M, int K, int HW, int group) {
+  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
+  if (HW % group || K % group) return MTR_E_SHAPE;
+  if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
+    return MTR_E_SHAPE;
+  return MTR_OK;
 }
 
 // VEC consecutive elements -> fp32 registers.  16-byte loads for f32x4, 8-byte for f16x4/bf16x4.

@@ -83,8 +83,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
         t = *reinterpret_cast<const float4*>(xsrc + (long long)k * HW);
         if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits
           const float bi = in_bias[k];
-          t.x = settled(activate<PRE>(t.x + bi)); t.y = settled(activate<PRE>(t.y + bi));
-          t.z = settled(activate<PRE>(t.z + bi)); t.w = settled(activate<PRE>(t.w + bi));
+          t.x = input_prologue<PRE>(t.x, bi); t.y = input_prologue<PRE>(t.y, bi);
+          t.z = input_prologue<PRE>(t.z, bi); t.w = input_prologue<PRE>(t.w, bi);
         }
         if (gsrc) {  // the squeeze-excite gate, once per staged element: x * g rounded as torch does
           const float g = gsrc[k];
@@ -165,16 +165,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_kernel(
         if (col >= n_total) continue;
         const unsigned b = fastdiv((unsigned)col, by_hw);
         const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
-        float4 r;
-        r.x = activate<ACT>(acc[i][j][4 * g + 0] + bm);
-        r.y = activate<ACT>(acc[i][j][4 * g + 1] + bm);
-        r.z = activate<ACT>(acc[i][j][4 * g + 2] + bm);
-        r.w = activate<ACT>(acc[i][j][4 * g + 3] + bm);
-        if (residual) {  // the block's skip connection, added after the activation (K10's order)
-          const float4 q = *reinterpret_cast<const float4*>(residual + off);
-          r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-        }
-        *reinterpret_cast<float4*>(y + off) = r;
+        epilogue_store4<ACT>(acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], bm,
+                             residual, y, off);
       }
     }
   }
@@ -266,8 +258,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
     float v0 = rx[P][0], v1 = rx[P][XV - 1];
     if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits.  A clamped
       // load may give anything here (inf, NaN): it is selected away below, never multiplied to zero
-      v0 = settled(activate<PRE>(v0 + rbi[P]));
-      if constexpr (XV == 2) v1 = settled(activate<PRE>(v1 + rbi[P]));
+      v0 = input_prologue<PRE>(v0, rbi[P]);
+      if constexpr (XV == 2) v1 = input_prologue<PRE>(v1, rbi[P]);
     }
     if constexpr (XV == 2) {
       *reinterpret_cast<float2*>(xd) = make_float2(x_ok ? v0 * g : 0.0f, x_ok ? v1 * g : 0.0f);
@@ -349,16 +341,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_deepk_kernel(
     if (m >= M) continue;
     const float bm = bias[m];
     const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
-    float4 r;
-    r.x = activate<ACT>(acc[f][0] + bm);
-    r.y = activate<ACT>(acc[f][1] + bm);
-    r.z = activate<ACT>(acc[f][2] + bm);
-    r.w = activate<ACT>(acc[f][3] + bm);
-    if (residual) {  // the block's skip connection, added after the activation (K10's order)
-      const float4 q = *reinterpret_cast<const float4*>(residual + off);
-      r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-    }
-    *reinterpret_cast<float4*>(y + off) = r;
+    epilogue_store4<ACT>(acc[f][0], acc[f][1], acc[f][2], acc[f][3], bm, residual, y, off);
   }
 }
 
@@ -449,8 +432,8 @@ __global__ __launch_bounds__(64 * kD6Waves) void conv1x1_deep64_kernel(
     if constexpr (PRE >= 0) {  // the epilogue of the convolution in front: K10's expression, K10's bits.  A clamped
       // load may give anything here (inf, NaN): it is selected away below, never multiplied to zero
       const float bi = rbi[P];
-      v.x = settled(activate<PRE>(v.x + bi)); v.y = settled(activate<PRE>(v.y + bi));
-      v.z = settled(activate<PRE>(v.z + bi)); v.w = settled(activate<PRE>(v.w + bi));
+      v.x = input_prologue<PRE>(v.x, bi); v.y = input_prologue<PRE>(v.y, bi);
+      v.z = input_prologue<PRE>(v.z, bi); v.w = input_prologue<PRE>(v.w, bi);
     }
     v.x = x_ok ? v.x * g : 0.0f; v.y = x_ok ? v.y * g : 0.0f; v.z = x_ok ? v.z * g : 0.0f; v.w = x_ok ? v.w * g : 0.0f;
     *reinterpret_cast<float4*>(&xs[stage * XS + xdst]) = v;
@@ -528,16 +511,7 @@ __global__ __launch_bounds__(64 * kD6Waves) void conv1x1_deep64_kernel(
     if (m >= M) continue;
     const float bm = bias[m];
     const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
-    float4 r;
-    r.x = activate<ACT>(acc[f][0] + bm);
-    r.y = activate<ACT>(acc[f][1] + bm);
-    r.z = activate<ACT>(acc[f][2] + bm);
-    r.w = activate<ACT>(acc[f][3] + bm);
-    if (residual) {  // the block's skip connection, added after the activation (K10's order)
-      const float4 q = *reinterpret_cast<const float4*>(residual + off);
-      r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-    }
-    *reinterpret_cast<float4*>(y + off) = r;
+    epilogue_store4<ACT>(acc[f][0], acc[f][1], acc[f][2], acc[f][3], bm, residual, y, off);
   }
 }
 
@@ -610,7 +584,7 @@ __global__ __launch_bounds__(64 * kStWaves) void conv1x1_stream_kernel(
       const int k = c * (2 * kStR) + 2 * j;
       float v = xr[j];
       // the epilogue of the convolution in front: K10's expression, K10's bits
-      if constexpr (PRE >= 0) v = settled(activate<PRE>(v + bs[k + half]));
+      if constexpr (PRE >= 0) v = input_prologue<PRE>(v, bs[k + half]);
       if constexpr (GATE) v *= gr[j];  // the squeeze-excite gate: x * g rounded as torch does
       v = (ok && k < K) ? v : 0.0f;
       const float* wb_ = &ws[(k + half) * LDW + l32];
@@ -649,8 +623,8 @@ __global__ __launch_bounds__(64 * kStWaves) void conv1x1_stream_kernel(
     if (c < n_chunks) multiply_chunk(c, xa, ga);
 
     // epilogue: lane holds channel m = .. + l32, positions 8 g + 4 half + 0..3 of the tile
-    auto epilogue = [&](auto act_c) {
-      constexpr int ACT = decltype(act_c)::value;
+    auto epilogue = [&](auto tag) {
+      constexpr int ACT = decltype(tag)::value;
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const int m = i * 32 + l32;
@@ -662,25 +636,12 @@ __global__ __launch_bounds__(64 * kStWaves) void conv1x1_stream_kernel(
           if (col >= n_total) continue;
           const unsigned b = fastdiv((unsigned)col, by_hw);
           const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
-          float4 r;
-          r.x = activate<ACT>(acc[i][4 * g + 0] + bm);
-          r.y = activate<ACT>(acc[i][4 * g + 1] + bm);
-          r.z = activate<ACT>(acc[i][4 * g + 2] + bm);
-          r.w = activate<ACT>(acc[i][4 * g + 3] + bm);
-          if (residual) {  // the block's skip connection, added after the activation (K10's order)
-            const float4 q = *reinterpret_cast<const float4*>(residual + off);
-            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-          }
-          *reinterpret_cast<float4*>(y + off) = r;
+          epilogue_store4<ACT>(acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3], bm, residual,
+                               y, off);
         }
       }
     };
-    switch (act) {
-      case kActRelu: epilogue(std::integral_constant<int, kActRelu>{}); break;
-      case kActSilu: epilogue(std::integral_constant<int, kActSilu>{}); break;
-      case kActHardswish: epilogue(std::integral_constant<int, kActHardswish>{}); break;
-      default: epilogue(std::integral_constant<int, kActNone>{}); break;
-    }
+    with_act(act, epilogue);
 
     tile += kStWaves;
     if (tile >= kStWaves * tiles) break;
@@ -781,181 +742,71 @@ inline int plan_for(int M, int K, int HW, long long B, int config, Conv1x1Plan* 
   }
 }
 
-// PRE: the kernels' template parameter (-1: no prologue, in_bias is NULL; else the input activation's code)
-template <int WM, int WN, int FM, int FN, int BK, int PRE>
-static int launch_conv1x1_pre(const float* x, const float* w, const float* bias, const float* in_bias,
-                              const float* gate, const float* residual, float* y, int act, int M, int K, int HW,
-                              long long n_total, hipStream_t stream) {
-  constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
-  const long long gx = (n_total + BN - 1) / BN, gy = (M + BM - 1) / BM;
+// One K13 launch's arguments, as the entry point has checked them
+struct Conv1x1Args {
+  const float *x, *w, *bias, *in_bias, *gate, *residual;
+  float* y;
+  int act, in_act, M, K, HW;
+  long long n_total;
+  hipStream_t stream;
+};
+
+// Launches `kern` on a grid of bm-channel x bn-column tiles; `extra`: the kernel's arguments behind by_hw (stream's)
+template <typename Kern, typename... Extra>
+static int launch_conv1x1(Kern kern, const Conv1x1Args& a, int bm, int bn, int threads, size_t lds, Extra... extra) {
+  const long long gx = (a.n_total + bn - 1) / bn, gy = (a.M + bm - 1) / bm;
   if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WM * WN);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-  MTR_CLEAR_STALE();
-#define MTR_C1_LAUNCH(ACT)                                                                                      \
-  hipLaunchKernelGGL((conv1x1_kernel<WM, WN, FM, FN, BK, ACT, PRE>), grid, block, 0, stream, x, w, bias, in_bias, \
-                     gate, residual, y, M, K, HW, (int)n_total, by_hw)
-  switch (act) {
-    case kActNone: MTR_C1_LAUNCH(kActNone); break;
-    case kActRelu: MTR_C1_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_C1_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_C1_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
+  if (lds > 64 * 1024) {
+    const int e = allow_dynamic_lds((const void*)kern, lds);
+    if (e != MTR_OK) return e;
   }
-#undef MTR_C1_LAUNCH
+  MTR_CLEAR_STALE();
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(threads), lds, a.stream, a.x, a.w, a.bias, a.in_bias,
+                     a.gate, a.residual, a.y, a.M, a.K, a.HW, (int)a.n_total, make_fastdiv((unsigned)a.HW), extra...);
   MTR_CHECK_LAUNCH();
   return MTR_OK;
+}
+
+// f(pre, act): the tags of the kernels' template parameters PRE (-1: no prologue, in_bias is NULL) and ACT
+template <typename F>
+static int dispatch_pre_act(const Conv1x1Args& a, F&& f) {
+  return dispatch_pre(a.in_bias, a.in_act,
+                      [&](auto pre) { return dispatch_act(a.act, [&](auto act) { return f(pre, act); }); });
 }
 
 template <int WM, int WN, int FM, int FN, int BK>
-static int launch_conv1x1_cfg(const float* x, const float* w, const float* bias, const float* in_bias, int in_act,
-                              const float* gate, const float* residual, float* y, int act, int M, int K, int HW,
-                              long long n_total, hipStream_t stream) {
-#define MTR_C1_PRE(PRE) \
-  launch_conv1x1_pre<WM, WN, FM, FN, BK, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
-  switch (in_bias ? in_act : -1) {
-    case -1: return MTR_C1_PRE(-1);
-    case kActNone: return MTR_C1_PRE(kActNone);
-    case kActRelu: return MTR_C1_PRE(kActRelu);
-    case kActSilu: return MTR_C1_PRE(kActSilu);
-    case kActHardswish: return MTR_C1_PRE(kActHardswish);
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_C1_PRE
-}
-
-template <int WAVES, int PRE>
-static int launch_conv1x1_deepk_pre(const float* x, const float* w, const float* bias, const float* in_bias,
-                                    const float* gate, const float* residual, float* y, int act, int M, int K,
-                                    int HW, long long n_total, hipStream_t stream) {
-  constexpr int BM = 32 * WAVES;
-  constexpr size_t lds = deepk_lds_bytes(WAVES);
-  const long long gx = (n_total + kDkBN - 1) / kDkBN, gy = (M + BM - 1) / BM;
-  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WAVES);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-#define MTR_DK_LAUNCH(ACT)                                                                                 \
-  do {                                                                                                     \
-    if (lds > 64 * 1024) {                                                                                 \
-      const int e = allow_dynamic_lds((const void*)conv1x1_deepk_kernel<WAVES, ACT, PRE>, lds);            \
-      if (e != MTR_OK) return e;                                                                           \
-    }                                                                                                      \
-    MTR_CLEAR_STALE();                                                                                     \
-    hipLaunchKernelGGL((conv1x1_deepk_kernel<WAVES, ACT, PRE>), grid, block, lds, stream, x, w, bias,      \
-                       in_bias, gate, residual, y, M, K, HW, (int)n_total, by_hw);                         \
-  } while (0)
-  switch (act) {
-    case kActNone: MTR_DK_LAUNCH(kActNone); break;
-    case kActRelu: MTR_DK_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_DK_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_DK_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_DK_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+static int launch_tiles(const Conv1x1Args& a) {
+  return dispatch_pre_act(a, [&](auto pre, auto act) {
+    return launch_conv1x1(conv1x1_kernel<WM, WN, FM, FN, BK, decltype(act)::value, decltype(pre)::value>, a,
+                          32 * FM * WM, 32 * FN * WN, 64 * WM * WN, 0);
+  });
 }
 
 template <int WAVES>
-static int launch_conv1x1_deepk(const float* x, const float* w, const float* bias, const float* in_bias,
-                                int in_act, const float* gate, const float* residual, float* y, int act, int M,
-                                int K, int HW, long long n_total, hipStream_t stream) {
-#define MTR_DK_PRE(PRE) \
-  launch_conv1x1_deepk_pre<WAVES, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
-  switch (in_bias ? in_act : -1) {
-    case -1: return MTR_DK_PRE(-1);
-    case kActNone: return MTR_DK_PRE(kActNone);
-    case kActRelu: return MTR_DK_PRE(kActRelu);
-    case kActSilu: return MTR_DK_PRE(kActSilu);
-    case kActHardswish: return MTR_DK_PRE(kActHardswish);
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_DK_PRE
+static int launch_deepk(const Conv1x1Args& a) {
+  return dispatch_pre_act(a, [&](auto pre, auto act) {
+    return launch_conv1x1(conv1x1_deepk_kernel<WAVES, decltype(act)::value, decltype(pre)::value>, a, 32 * WAVES,
+                          kDkBN, 64 * WAVES, deepk_lds_bytes(WAVES));
+  });
 }
 
-template <int PRE>
-static int launch_conv1x1_deep64_pre(const float* x, const float* w, const float* bias, const float* in_bias,
-                                     const float* gate, const float* residual, float* y, int act, int M, int K,
-                                     int HW, long long n_total, hipStream_t stream) {
-  const long long gx = (n_total + kD6BN - 1) / kD6BN, gy = (M + kD6BM - 1) / kD6BM;
-  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * kD6Waves);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-  MTR_CLEAR_STALE();
-#define MTR_D6_LAUNCH(ACT)                                                                                    \
-  hipLaunchKernelGGL((conv1x1_deep64_kernel<ACT, PRE>), grid, block, 0, stream, x, w, bias, in_bias, gate,    \
-                     residual, y, M, K, HW, (int)n_total, by_hw)
-  switch (act) {
-    case kActNone: MTR_D6_LAUNCH(kActNone); break;
-    case kActRelu: MTR_D6_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_D6_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_D6_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_D6_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+static int launch_deep64(const Conv1x1Args& a) {
+  return dispatch_pre_act(a, [&](auto pre, auto act) {
+    return launch_conv1x1(conv1x1_deep64_kernel<decltype(act)::value, decltype(pre)::value>, a, kD6BM, kD6BN,
+                          64 * kD6Waves, 0);
+  });
 }
 
-static int launch_conv1x1_deep64(const float* x, const float* w, const float* bias, const float* in_bias,
-                                 int in_act, const float* gate, const float* residual, float* y, int act, int M,
-                                 int K, int HW, long long n_total, hipStream_t stream) {
-#define MTR_D6_PRE(PRE) \
-  launch_conv1x1_deep64_pre<PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, stream)
-  switch (in_bias ? in_act : -1) {
-    case -1: return MTR_D6_PRE(-1);
-    case kActNone: return MTR_D6_PRE(kActNone);
-    case kActRelu: return MTR_D6_PRE(kActRelu);
-    case kActSilu: return MTR_D6_PRE(kActSilu);
-    case kActHardswish: return MTR_D6_PRE(kActHardswish);
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_D6_PRE
-}
-
-template <int MT, int PRE>
-static int launch_conv1x1_stream_pre(const float* x, const float* w, const float* bias, const float* in_bias,
-                                     const float* gate, const float* residual, float* y, int act, int M, int K,
-                                     int HW, long long n_total, int bn, hipStream_t stream) {
-  const int kpad = stream_kpad(K);
-  const size_t lds = ((size_t)kpad * 32 * MT + (PRE >= 0 ? kpad : 0)) * sizeof(float);
-  const long long gx = (n_total + bn - 1) / bn;
-  if (gx > 0x7fffffffLL) return MTR_E_SHAPE;
-  if (act < kActNone || act > kActHardswish) return MTR_E_PARAM;
-  const dim3 grid((unsigned)gx), block(64 * kStWaves);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-#define MTR_ST_LAUNCH(GATE)                                                                               \
-  do {                                                                                                    \
-    if (lds > 64 * 1024) {                                                                                \
-      const int e = allow_dynamic_lds((const void*)conv1x1_stream_kernel<MT, PRE, GATE>, lds);            \
-      if (e != MTR_OK) return e;                                                                          \
-    }                                                                                                     \
-    MTR_CLEAR_STALE();                                                                                    \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<MT, PRE, GATE>), grid, block, lds, stream, x, w, bias,      \
-                       in_bias, gate, residual, y, M, K, HW, (int)n_total, by_hw, act,                    \
-                       bn / (32 * kStWaves));                                                             \
-  } while (0)
-  if (gate) MTR_ST_LAUNCH(true); else MTR_ST_LAUNCH(false);
-#undef MTR_ST_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
-}
-
+// bn: the plan's columns per workgroup, 128 per pass (one grid row: every wave holds all MT row tiles)
 template <int MT>
-static int launch_conv1x1_stream(const float* x, const float* w, const float* bias, const float* in_bias,
-                                 int in_act, const float* gate, const float* residual, float* y, int act, int M,
-                                 int K, int HW, long long n_total, int bn, hipStream_t stream) {
-#define MTR_ST_PRE(PRE) \
-  launch_conv1x1_stream_pre<MT, PRE>(x, w, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, bn, stream)
-  switch (in_bias ? in_act : -1) {
-    case -1: return MTR_ST_PRE(-1);
-    case kActNone: return MTR_ST_PRE(kActNone);
-    case kActRelu: return MTR_ST_PRE(kActRelu);
-    case kActSilu: return MTR_ST_PRE(kActSilu);
-    case kActHardswish: return MTR_ST_PRE(kActHardswish);
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_ST_PRE
+static int launch_stream(const Conv1x1Args& a, int bn) {
+  return dispatch_pre(a.in_bias, a.in_act, [&](auto pre) {
+    constexpr int PRE = decltype(pre)::value;
+    const int kpad = stream_kpad(a.K), tiles = bn / (32 * kStWaves);
+    const size_t lds = ((size_t)kpad * 32 * MT + (PRE >= 0 ? kpad : 0)) * sizeof(float);
+    const auto go = [&](auto kern) { return launch_conv1x1(kern, a, 32 * MT, bn, 64 * kStWaves, lds, a.act, tiles); };
+    return a.gate ? go(conv1x1_stream_kernel<MT, PRE, true>) : go(conv1x1_stream_kernel<MT, PRE, false>);
+  });
 }
 
 }  // namespace mtr
@@ -991,11 +842,8 @@ extern "C" int mtr_conv1x1_bias_act_pre(const void* x, int dtype, const float* w
                                         int config) {
   if (!x || !weight || !bias || !y) return MTR_E_NULL;
   if (dtype != MTR_F32) return MTR_E_DTYPE;
-  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
   // 16-byte groups: four positions of x / y / residual, four k of a weight row
-  if (HW % 4 || K % 4) return MTR_E_SHAPE;
-  if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
-    return MTR_E_SHAPE;
+  if (mtr::conv1x1_shape_check(B, M, K, HW, 4) != MTR_OK) return MTR_E_SHAPE;
   if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
   if (in_act < mtr::kActNone || in_act > mtr::kActHardswish) return MTR_E_PARAM;
   if (!in_bias && in_act != mtr::kActNone) return MTR_E_PARAM;  // an input activation belongs to an input bias
@@ -1004,39 +852,32 @@ extern "C" int mtr_conv1x1_bias_act_pre(const void* x, int dtype, const float* w
     return MTR_E_ALIGN;
   if (x == y || (residual && residual == x)) return MTR_E_PARAM;  // y is written while x is still read
   if (B == 0) return MTR_OK;
-  const float* xf = (const float*)x;
-  const float* rf = (const float*)residual;
-  float* yf = (float*)y;
-  const long long n_total = B * HW;
-  hipStream_t s = (hipStream_t)stream;
+  const mtr::Conv1x1Args a = {(const float*)x, weight, bias, in_bias, gate, (const float*)residual, (float*)y,
+                               act, in_act, M, K, HW, B * HW, (hipStream_t)stream};
   mtr::Conv1x1Plan p;
   if (mtr::plan_for(M, K, HW, B, config, &p) != MTR_OK) return MTR_E_PARAM;
-#define MTR_C1_ARGS xf, weight, bias, in_bias, in_act, gate, rf, yf, act, M, K, HW, n_total, s
-#define MTR_C1_ARGS_ST xf, weight, bias, in_bias, in_act, gate, rf, yf, act, M, K, HW, n_total, p.bn, s
   switch (p.cfg) {
-    case mtr::kCfgWide: return mtr::launch_conv1x1_cfg<2, 2, 3, 2, 16>(MTR_C1_ARGS);
-    case mtr::kCfgSquare: return mtr::launch_conv1x1_cfg<2, 2, 2, 2, 16>(MTR_C1_ARGS);
+    case mtr::kCfgWide: return mtr::launch_tiles<2, 2, 3, 2, 16>(a);
+    case mtr::kCfgSquare: return mtr::launch_tiles<2, 2, 2, 2, 16>(a);
     case mtr::kCfgStream:
       switch (p.waves_m) {
-        case 1: return mtr::launch_conv1x1_stream<1>(MTR_C1_ARGS_ST);
-        case 2: return mtr::launch_conv1x1_stream<2>(MTR_C1_ARGS_ST);
-        default: return mtr::launch_conv1x1_stream<3>(MTR_C1_ARGS_ST);
+        case 1: return mtr::launch_stream<1>(a, p.bn);
+        case 2: return mtr::launch_stream<2>(a, p.bn);
+        default: return mtr::launch_stream<3>(a, p.bn);
       }
-    case mtr::kCfgDeep64: return mtr::launch_conv1x1_deep64(MTR_C1_ARGS);
+    case mtr::kCfgDeep64: return mtr::launch_deep64(a);
     case mtr::kCfgDeepK:
       switch (p.waves_m) {
-        case 4: return mtr::launch_conv1x1_deepk<4>(MTR_C1_ARGS);
-        default: return mtr::launch_conv1x1_deepk<8>(MTR_C1_ARGS);
+        case 4: return mtr::launch_deepk<4>(a);
+        default: return mtr::launch_deepk<8>(a);
       }
     default:
       switch (p.waves_m) {
-        case 1: return mtr::launch_conv1x1_cfg<1, 1, 1, 1, 16>(MTR_C1_ARGS);
-        case 2: return mtr::launch_conv1x1_cfg<2, 1, 1, 1, 16>(MTR_C1_ARGS);
-        case 3: return mtr::launch_conv1x1_cfg<3, 1, 1, 1, 16>(MTR_C1_ARGS);
-        case 4: return mtr::launch_conv1x1_cfg<4, 1, 1, 1, 32>(MTR_C1_ARGS);
-        default: return mtr::launch_conv1x1_cfg<5, 1, 1, 1, 16>(MTR_C1_ARGS);
+        case 1: return mtr::launch_tiles<1, 1, 1, 1, 16>(a);
+        case 2: return mtr::launch_tiles<2, 1, 1, 1, 16>(a);
+        case 3: return mtr::launch_tiles<3, 1, 1, 1, 16>(a);
+        case 4: return mtr::launch_tiles<4, 1, 1, 1, 32>(a);
+        default: return mtr::launch_tiles<5, 1, 1, 1, 16>(a);
       }
   }
-#undef MTR_C1_ARGS
-#undef MTR_C1_ARGS_ST
 }

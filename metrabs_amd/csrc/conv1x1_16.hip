@@ -55,8 +55,6 @@ template <> struct Bits16<MTR_BF16> {
   }
 };
 
-template <int V> struct ActTag { static constexpr int value = V; };
-
 constexpr int kC16Pad = 8;  // X^T image row pad (16-bit elements): rows (BK + 8) * 2 bytes apart
 
 // WM x WN waves, each FM x FN tiles of 32 x 32 (channels x positions), k-tiles of BK
@@ -214,7 +212,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv1x1_16_kernel(
       }
     }
   };
-  switch (act) {  // wave-uniform: one epilogue body per activation, the GEMM shared
+  // wave-uniform: one epilogue body per activation, the GEMM shared.  Written out: behind the shared with_act() the
+  // compiler forms the epilogue's column indices another way, four instructions more
+  switch (act) {
     case kActRelu: epilogue(ActTag<kActRelu>()); break;
     case kActSilu: epilogue(ActTag<kActSilu>()); break;
     case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
@@ -429,12 +429,7 @@ __global__ __launch_bounds__(256) void conv1x1_16_deepk_kernel(
       *reinterpret_cast<uint4*>(y + off) = __builtin_bit_cast(uint4, o);
     }
   };
-  switch (act) {
-    case kActRelu: epilogue(ActTag<kActRelu>()); break;
-    case kActSilu: epilogue(ActTag<kActSilu>()); break;
-    case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
-    default: epilogue(ActTag<kActNone>()); break;
-  }
+  with_act(act, epilogue);
 }
 
 // The tile table, chosen from the shape only:
@@ -467,57 +462,49 @@ inline int plan_for16(int M, int K, int config, Conv1x1Plan16* p) {
   }
 }
 
+// One K13h launch's arguments, as the entry point has checked them
+struct Conv1x1Args16 {
+  const unsigned short *x, *w;
+  const float *bias, *gate;
+  const unsigned short* residual;
+  unsigned short* y;
+  int act, M, K, HW;
+  long long n_total;
+  hipStream_t stream;
+};
+
+// Launches `kern` on a grid of bm-channel x bn-column tiles
+template <typename Kern>
+static int launch_conv1x1_16(Kern kern, const Conv1x1Args16& a, int bm, int bn, int threads) {
+  const long long gx = (a.n_total + bn - 1) / bn, gy = (a.M + bm - 1) / bm;
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  MTR_CLEAR_STALE();
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(threads), 0, a.stream, a.x, a.w, a.bias, a.gate,
+                     a.residual, a.y, a.M, a.K, a.HW, (int)a.n_total, make_fastdiv((unsigned)a.HW), a.act);
+  MTR_CHECK_LAUNCH();
+  return MTR_OK;
+}
+
 template <int DT, int WM, int WN, int FM, int FN, int BK>
-static int launch_conv1x1_16_cfg(const void* x, const void* w, const float* bias, const float* gate,
-                                 const void* residual, void* y, int act, int M, int K, int HW, long long n_total,
-                                 hipStream_t stream) {
-  constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
-  const long long gx = (n_total + BN - 1) / BN, gy = (M + BM - 1) / BM;
-  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  const dim3 grid((unsigned)gx, (unsigned)gy), block(64 * WM * WN);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-  MTR_CLEAR_STALE();
-  hipLaunchKernelGGL((conv1x1_16_kernel<DT, WM, WN, FM, FN, BK>), grid, block, 0, stream,
-                     (const unsigned short*)x, (const unsigned short*)w, bias, gate, (const unsigned short*)residual,
-                     (unsigned short*)y, M, K, HW, (int)n_total, by_hw, act);
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+static int launch_tiles16(const Conv1x1Args16& a) {
+  return launch_conv1x1_16(conv1x1_16_kernel<DT, WM, WN, FM, FN, BK>, a, 32 * FM * WM, 32 * FN * WN, 64 * WM * WN);
 }
 
+// the only place that maps a plan to template parameters
 template <int DT>
-static int launch_conv1x1_16_deepk(const void* x, const void* w, const float* bias, const float* gate,
-                                   const void* residual, void* y, int act, int M, int K, int HW, long long n_total,
-                                   hipStream_t stream) {
-  const long long gx = (n_total + kDk16BN - 1) / kDk16BN, gy = (M + kDk16BM - 1) / kDk16BM;
-  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  const dim3 grid((unsigned)gx, (unsigned)gy), block(256);
-  const FastDiv by_hw = make_fastdiv((unsigned)HW);
-  MTR_CLEAR_STALE();
-#define MTR_DK16_LAUNCH(GATE)                                                                                        \
-  hipLaunchKernelGGL((conv1x1_16_deepk_kernel<DT, GATE>), grid, block, 0, stream, (const unsigned short*)x,          \
-                     (const unsigned short*)w, bias, gate, (const unsigned short*)residual, (unsigned short*)y, M, K, \
-                     HW, (int)n_total, by_hw, act)
-  if (gate) MTR_DK16_LAUNCH(true); else MTR_DK16_LAUNCH(false);
-#undef MTR_DK16_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
-}
-
-template <int DT>
-static int launch_conv1x1_16(const void* x, const void* w, const float* bias, const float* gate, const void* residual,
-                             void* y, int act, int M, int K, int HW, long long n_total, int config, hipStream_t s) {
+static int launch_plan16(const Conv1x1Args16& a, int config) {
   Conv1x1Plan16 p;
-  if (plan_for16(M, K, config, &p) != MTR_OK) return MTR_E_PARAM;
+  if (plan_for16(a.M, a.K, config, &p) != MTR_OK) return MTR_E_PARAM;
   if (p.cfg == kCfg16DeepK)
-    return launch_conv1x1_16_deepk<DT>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
-  if (p.cfg == kCfg16Square)
-    return launch_conv1x1_16_cfg<DT, 2, 2, 2, 2, 32>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    return a.gate ? launch_conv1x1_16(conv1x1_16_deepk_kernel<DT, true>, a, kDk16BM, kDk16BN, 256)
+                  : launch_conv1x1_16(conv1x1_16_deepk_kernel<DT, false>, a, kDk16BM, kDk16BN, 256);
+  if (p.cfg == kCfg16Square) return launch_tiles16<DT, 2, 2, 2, 2, 32>(a);
   switch (p.waves_m) {
-    case 1: return launch_conv1x1_16_cfg<DT, 1, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
-    case 2: return launch_conv1x1_16_cfg<DT, 2, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
-    case 3: return launch_conv1x1_16_cfg<DT, 3, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
-    case 4: return launch_conv1x1_16_cfg<DT, 4, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
-    default: return launch_conv1x1_16_cfg<DT, 5, 1, 1, 1, 64>(x, w, bias, gate, residual, y, act, M, K, HW, n_total, s);
+    case 1: return launch_tiles16<DT, 1, 1, 1, 1, 64>(a);
+    case 2: return launch_tiles16<DT, 2, 1, 1, 1, 64>(a);
+    case 3: return launch_tiles16<DT, 3, 1, 1, 1, 64>(a);
+    case 4: return launch_tiles16<DT, 4, 1, 1, 1, 64>(a);
+    default: return launch_tiles16<DT, 5, 1, 1, 1, 64>(a);
   }
 }
 
@@ -547,11 +534,8 @@ extern "C" int mtr_conv1x1_bias_act16_opts(const void* x, int dtype, const void*
                                            int K, int HW, void* y, mtr_stream_t stream, int config) {
   if (!x || !weight || !bias || !y) return MTR_E_NULL;
   if (dtype != MTR_F16 && dtype != MTR_BF16) return MTR_E_DTYPE;
-  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
   // 16-byte groups: eight positions of a k-row of x, eight k of a weight row
-  if (HW % 8 || K % 8) return MTR_E_SHAPE;
-  if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
-    return MTR_E_SHAPE;
+  if (mtr::conv1x1_shape_check(B, M, K, HW, 8) != MTR_OK) return MTR_E_SHAPE;
   if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
   if (config < -1 || config > mtr::kCfg16DeepK) return MTR_E_PARAM;
   if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
@@ -559,8 +543,8 @@ extern "C" int mtr_conv1x1_bias_act16_opts(const void* x, int dtype, const void*
     return MTR_E_ALIGN;
   if (x == y || (residual && residual == x)) return MTR_E_PARAM;  // y is written while x is still read
   if (B == 0) return MTR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MTR_F16)
-    return mtr::launch_conv1x1_16<MTR_F16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, config, s);
-  return mtr::launch_conv1x1_16<MTR_BF16>(x, weight, bias, gate, residual, y, act, M, K, HW, B * HW, config, s);
+  const mtr::Conv1x1Args16 a = {(const unsigned short*)x, (const unsigned short*)weight, bias, gate,
+                                 (const unsigned short*)residual, (unsigned short*)y, act, M, K, HW, B * HW,
+                                 (hipStream_t)stream};
+  return dtype == MTR_F16 ? mtr::launch_plan16<MTR_F16>(a, config) : mtr::launch_plan16<MTR_BF16>(a, config);
 }

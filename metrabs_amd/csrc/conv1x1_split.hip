@@ -78,12 +78,6 @@ __device__ __forceinline__ void sp_split2(float a, float b, unsigned (&out)[3]) 
   }
 }
 
-template <int PRE>
-__device__ __forceinline__ float sp_prologue(float v, float bi) {
-  if constexpr (PRE >= 0) return settled(activate<PRE>(v + bi));  // K10's expression, K10's bits (as K13 stages them)
-  return v;
-}
-
 template <int MT, int PRE, bool GATE>
 __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
     const float* __restrict__ x, const uint4* __restrict__ ws, const float* __restrict__ bias,
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
       const float t[4] = {xr[S][r].x, xr[S][r].y, xr[S][r].z, xr[S][r].w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float e = sp_prologue<PRE>(t[i], xbi[S][r]);
+        float e = input_prologue<PRE>(t[i], xbi[S][r]);
         if constexpr (GATE) e *= xg[S][r];  // the squeeze-excite gate: x * g rounded to f32 as torch does, then split
         v[r][i] = xr_ok[S] ? e : 0.0f;      // a column past B * HW or a k past K: zeros, whatever the prologue
       }
@@ -231,8 +225,8 @@ __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
   }
 
   // ---- epilogue: lane holds channel 16 mt + fr, positions n0 + 16 j + 4 fq + 0 .. 3
-  auto epilogue = [&](auto act_c) {
-    constexpr int ACT = decltype(act_c)::value;
+  auto epilogue = [&](auto tag) {
+    constexpr int ACT = decltype(tag)::value;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int m = (mt0 + kSpWaves * i) * 16 + fr;
@@ -244,25 +238,12 @@ __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
         if (col >= n_total) continue;
         const unsigned b = fastdiv((unsigned)col, by_hw);
         const long long off = ((long long)b * M + m) * HW + (col - (int)b * HW);
-        float4 r;
-        r.x = activate<ACT>(acc[i][j][0] + bm);
-        r.y = activate<ACT>(acc[i][j][1] + bm);
-        r.z = activate<ACT>(acc[i][j][2] + bm);
-        r.w = activate<ACT>(acc[i][j][3] + bm);
-        if (residual) {  // the block's skip connection, added after the activation (K10's order)
-          const float4 q = *reinterpret_cast<const float4*>(residual + off);
-          r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-        }
-        *reinterpret_cast<float4*>(y + off) = r;
+        epilogue_store4<ACT>(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], bm, residual, y, off);
       }
     }
   };
-  switch (act) {  // (a run-time code: the activation is a few instructions of the epilogue, not worth 4 x the kernels)
-    case kActRelu: epilogue(std::integral_constant<int, kActRelu>{}); break;
-    case kActSilu: epilogue(std::integral_constant<int, kActSilu>{}); break;
-    case kActHardswish: epilogue(std::integral_constant<int, kActHardswish>{}); break;
-    default: epilogue(std::integral_constant<int, kActNone>{}); break;
-  }
+  // (a run-time code: the activation is a few instructions of the epilogue, not worth 4 x the kernels)
+  with_act(act, epilogue);
 }
 
 // 16-channel tiles per wave: all of the layer's (at most 4: 256 channels per workgroup) while the grid has a
@@ -276,58 +257,41 @@ static int split_tiles_per_wave(int M, long long n_total) {
   return mt;
 }
 
-template <int MT, int PRE, bool GATE>
-static int launch_split_gate(const float* x, const void* ws, const float* bias, const float* in_bias, const float* gate,
-                        const float* residual, float* y, int act, int M, int K, int HW, long long n_total,
-                        hipStream_t s) {
-  const int Kp = (K + 31) / 32 * 32;
-  const int n_mt = (M + 15) / 16;
-  const long long gx = (n_total + kSpBN - 1) / kSpBN, gy = (n_mt + kSpWaves * MT - 1) / (kSpWaves * MT);
-  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
-  MTR_CLEAR_STALE();
-  hipLaunchKernelGGL((conv1x1_split_kernel<MT, PRE, GATE>), dim3((unsigned)gx, (unsigned)gy), dim3(kSpNT), 0, s, x,
-                     (const uint4*)ws, bias, in_bias, gate, residual, y, act, M, K, Kp, HW, (int)n_total,
-                     make_fastdiv((unsigned)HW));
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
-}
-
-template <int MT, int PRE>
-static int launch_split(const float* x, const void* ws, const float* bias, const float* in_bias, const float* gate,
-                        const float* residual, float* y, int act, int M, int K, int HW, long long n_total,
-                        hipStream_t s) {
-  return gate ? launch_split_gate<MT, PRE, true>(x, ws, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, s)
-              : launch_split_gate<MT, PRE, false>(x, ws, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, s);
-}
+// One K20 launch's arguments, as the entry point has checked them
+struct SplitArgs {
+  const float* x;
+  const void* ws;
+  const float *bias, *in_bias, *gate, *residual;
+  float* y;
+  int act, in_act, M, K, HW;
+  long long n_total;
+  hipStream_t stream;
+};
 
 template <int MT>
-static int launch_split_pre(const float* x, const void* ws, const float* bias, const float* in_bias, int in_act,
-                            const float* gate, const float* residual, float* y, int act, int M, int K, int HW,
-                            long long n_total, hipStream_t s) {
-#define MTR_SP_ARGS x, ws, bias, in_bias, gate, residual, y, act, M, K, HW, n_total, s
-  if (!in_bias) return launch_split<MT, -1>(MTR_SP_ARGS);
-  switch (in_act) {
-    case kActNone: return launch_split<MT, kActNone>(MTR_SP_ARGS);
-    case kActRelu: return launch_split<MT, kActRelu>(MTR_SP_ARGS);
-    case kActSilu: return launch_split<MT, kActSilu>(MTR_SP_ARGS);
-    case kActHardswish: return launch_split<MT, kActHardswish>(MTR_SP_ARGS);
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_SP_ARGS
-}
-
-static int split_shape_check(long long B, int M, int K, int HW) {
-  if (B < 0 || M <= 0 || K <= 0 || HW <= 0) return MTR_E_SHAPE;
-  if (HW % 4 || K % 4) return MTR_E_SHAPE;  // 16-byte groups: four positions of x / y / residual
-  if (B * HW > 0x7fffffffLL || (long long)K * HW > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL)
-    return MTR_E_SHAPE;
-  return MTR_OK;
+static int launch_split(const SplitArgs& a) {
+  const int Kp = (a.K + 31) / 32 * 32;
+  const int n_mt = (a.M + 15) / 16;
+  const long long gx = (a.n_total + kSpBN - 1) / kSpBN, gy = (n_mt + kSpWaves * MT - 1) / (kSpWaves * MT);
+  if (gx > 0x7fffffffLL || gy > 65535) return MTR_E_SHAPE;
+  return dispatch_pre(a.in_bias, a.in_act, [&](auto pre) {
+    const auto go = [&](auto kern) -> int {
+      MTR_CLEAR_STALE();
+      hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(kSpNT), 0, a.stream, a.x, (const uint4*)a.ws,
+                         a.bias, a.in_bias, a.gate, a.residual, a.y, a.act, a.M, a.K, Kp, a.HW, (int)a.n_total,
+                         make_fastdiv((unsigned)a.HW));
+      MTR_CHECK_LAUNCH();
+      return MTR_OK;
+    };
+    constexpr int PRE = decltype(pre)::value;
+    return a.gate ? go(conv1x1_split_kernel<MT, PRE, true>) : go(conv1x1_split_kernel<MT, PRE, false>);
+  });
 }
 
 }  // namespace mtr
 
 extern "C" int mtr_conv1x1_split_supported(long long B, int M, int K, int HW) {
-  return mtr::split_shape_check(B, M, K, HW);
+  return mtr::conv1x1_shape_check(B, M, K, HW, 4);  // 16-byte groups: four positions of x / y / residual
 }
 
 extern "C" int mtr_conv1x1_bias_act_split(const void* x, const void* w_split, const float* bias,
@@ -335,7 +299,7 @@ extern "C" int mtr_conv1x1_bias_act_split(const void* x, const void* w_split, co
                                           const void* residual, int act, long long B, int M, int K, int HW,
                                           void* y, mtr_stream_t stream) {
   if (!x || !w_split || !bias || !y) return MTR_E_NULL;
-  const int e = mtr::split_shape_check(B, M, K, HW);
+  const int e = mtr::conv1x1_shape_check(B, M, K, HW, 4);
   if (e != MTR_OK) return e;
   if (act < mtr::kActNone || act > mtr::kActHardswish) return MTR_E_PARAM;
   if (in_act < mtr::kActNone || in_act > mtr::kActHardswish) return MTR_E_PARAM;
@@ -350,16 +314,12 @@ extern "C" int mtr_conv1x1_bias_act_split(const void* x, const void* w_split, co
   if (x == y || (residual && residual == x)) return MTR_E_PARAM;
   if (B > 0 && ((x0 < y1 && y0 < x1) || (residual && r0 < y1 && y0 < r1))) return MTR_E_PARAM;
   if (B == 0) return MTR_OK;
-  const long long n_total = B * HW;
-  hipStream_t s = (hipStream_t)stream;
-#define MTR_SP_CALL(MT)                                                                                          \
-  return mtr::launch_split_pre<MT>((const float*)x, w_split, bias, in_bias, in_act, gate, (const float*)residual, \
-                                   (float*)y, act, M, K, HW, n_total, s)
-  switch (mtr::split_tiles_per_wave(M, n_total)) {
-    case 1: MTR_SP_CALL(1);
-    case 2: MTR_SP_CALL(2);
-    case 3: MTR_SP_CALL(3);
-    default: MTR_SP_CALL(4);
+  const mtr::SplitArgs a = {(const float*)x, w_split, bias, in_bias, gate, (const float*)residual, (float*)y,
+                             act, in_act, M, K, HW, B * HW, (hipStream_t)stream};
+  switch (mtr::split_tiles_per_wave(M, a.n_total)) {
+    case 1: return mtr::launch_split<1>(a);
+    case 2: return mtr::launch_split<2>(a);
+    case 3: return mtr::launch_split<3>(a);
+    default: return mtr::launch_split<4>(a);
   }
-#undef MTR_SP_CALL
 }

@@ -58,8 +58,6 @@ template <> struct Conv3Bits<MTR_BF16> {
   }
 };
 
-template <int V> struct Conv3ActTag { static constexpr int value = V; };
-
 // the geometry of one launch, computed on the host (conv3x3_geometry) and used by both sides
 struct Conv3Geo {
   int Cin, M, H, W, Ho, Wo, stride;
@@ -261,11 +259,14 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_16_kernel(
       if (i + 1 < FM) __syncthreads();  // the rows are rewritten by the next channel tile
     }
   };
-  switch (act) {  // wave-uniform: one epilogue body per activation, the GEMM shared
-    case kActRelu: epilogue(Conv3ActTag<kActRelu>()); break;
-    case kActSilu: epilogue(Conv3ActTag<kActSilu>()); break;
-    case kActHardswish: epilogue(Conv3ActTag<kActHardswish>()); break;
-    default: epilogue(Conv3ActTag<kActNone>()); break;
+  // wave-uniform: one epilogue body per activation, the GEMM shared.  Written out: behind the shared with_act() the
+  // compiler lays the epilogue's branches out another way and two instantiations take two SGPRs more (DESIGN.md
+  // section 27)
+  switch (act) {
+    case kActRelu: epilogue(ActTag<kActRelu>()); break;
+    case kActSilu: epilogue(ActTag<kActSilu>()); break;
+    case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
+    default: epilogue(ActTag<kActNone>()); break;
   }
 }
 

@@ -47,8 +47,6 @@ constexpr int kWgLDV = 80;  // floats between the [xi][ci] rows of V: 64 tiles +
 constexpr int kWgLDU = 48;  // floats between the [xi][ci] rows of U: 32 channels + 16
 constexpr size_t kWgLdsBytes = (size_t)16 * kWgCK * (kWgLDV + kWgLDU) * sizeof(float);
 
-template <int V> struct WgActTag { static constexpr int value = V; };
-
 // the geometry of one launch, computed on the host (conv3x3_winograd_shape)
 struct WgGeo {
   int Cin, M, H, W;
@@ -211,12 +209,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_winograd_kernel(
       }
     }
   };
-  switch (act) {  // wave-uniform: one epilogue body per activation, the GEMM shared
-    case kActRelu: epilogue(WgActTag<kActRelu>()); break;
-    case kActSilu: epilogue(WgActTag<kActSilu>()); break;
-    case kActHardswish: epilogue(WgActTag<kActHardswish>()); break;
-    default: epilogue(WgActTag<kActNone>()); break;
-  }
+  with_act(act, epilogue);  // wave-uniform: one epilogue body per activation, the GEMM shared
 }
 
 // the shape rules of the entry (MTR_E_SHAPE: the caller takes the library path); fills g for B > 0

@@ -316,19 +316,12 @@ static int launch_depthwise(const void* x, const float* w, const float* bias, in
       const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
       const float inv = 1.0f / (float)(H * W);
       MTR_CLEAR_STALE();
-#define MTR_DW_BLOCK(A)                                                                            \
-  hipLaunchKernelGGL((depthwise3x3_s1_block_kernel<T, A>), grid, block, 0, stream, (const T*)x, w, \
-                     bias, (T*)y, row_mean, (int)n_planes, C, H, W, lp_log2, tw, inv)
-      switch (act) {
-        case kActNone: MTR_DW_BLOCK(kActNone); break;
-        case kActRelu: MTR_DW_BLOCK(kActRelu); break;
-        case kActSilu: MTR_DW_BLOCK(kActSilu); break;
-        case kActHardswish: MTR_DW_BLOCK(kActHardswish); break;
-        default: return MTR_E_PARAM;
-      }
-#undef MTR_DW_BLOCK
-      MTR_CHECK_LAUNCH();
-      return MTR_OK;
+      return dispatch_act(act, [&](auto tag) -> int {
+        hipLaunchKernelGGL((depthwise3x3_s1_block_kernel<T, decltype(tag)::value>), grid, block, 0, stream,
+                           (const T*)x, w, bias, (T*)y, row_mean, (int)n_planes, C, H, W, lp_log2, tw, inv);
+        MTR_CHECK_LAUNCH();
+        return MTR_OK;
+      });
     }
   }
   DwGeom g;
@@ -349,23 +342,17 @@ static int launch_depthwise(const void* x, const float* w, const float* bias, in
   const bool vec = (W & 3) == 0 && ((uintptr_t)x % 16) == 0 &&
                    (STRIDE == 1 ? (symmetric && pad == 1) : (OW * 2 == W && pad_left <= 1));
   MTR_CLEAR_STALE();
-#define MTR_DW_LAUNCH(A)                                                                            \
-  if (vec)                                                                                          \
-    hipLaunchKernelGGL((depthwise3x3_kernel<T, A, STRIDE, true>), grid, block, 0, stream, (const T*)x, \
-                       w, bias, (T*)y, row_mean, g);                                                \
-  else                                                                                              \
-    hipLaunchKernelGGL((depthwise3x3_kernel<T, A, STRIDE, false>), grid, block, 0, stream,          \
-                       (const T*)x, w, bias, (T*)y, row_mean, g)
-  switch (act) {
-    case kActNone: MTR_DW_LAUNCH(kActNone); break;
-    case kActRelu: MTR_DW_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_DW_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_DW_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_DW_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return dispatch_act(act, [&](auto tag) -> int {
+    constexpr int A = decltype(tag)::value;
+    if (vec)
+      hipLaunchKernelGGL((depthwise3x3_kernel<T, A, STRIDE, true>), grid, block, 0, stream, (const T*)x, w, bias,
+                         (T*)y, row_mean, g);
+    else
+      hipLaunchKernelGGL((depthwise3x3_kernel<T, A, STRIDE, false>), grid, block, 0, stream, (const T*)x, w, bias,
+                         (T*)y, row_mean, g);
+    MTR_CHECK_LAUNCH();
+    return MTR_OK;
+  });
 }
 
 template <typename T>

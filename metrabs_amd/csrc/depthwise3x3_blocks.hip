@@ -196,19 +196,12 @@ static int launch_depthwise_blocks(const void* x, const float* w, const float* b
   const dim3 grid((unsigned)n_wg), block(256);
   const size_t lds = row_mean ? (size_t)g.ppw * g.groups * sizeof(float) : 0;  // <= 16 KiB (128 x 128)
   MTR_CLEAR_STALE();
-#define MTR_DWB_LAUNCH(A)                                                                               \
-  hipLaunchKernelGGL((depthwise3x3_blocks_kernel<T, A, BC>), grid, block, lds, stream, (const T*)x, w, \
-                     bias, (T*)y, row_mean, g)
-  switch (act) {
-    case kActNone: MTR_DWB_LAUNCH(kActNone); break;
-    case kActRelu: MTR_DWB_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_DWB_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_DWB_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_DWB_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return dispatch_act(act, [&](auto tag) -> int {
+    hipLaunchKernelGGL((depthwise3x3_blocks_kernel<T, decltype(tag)::value, BC>), grid, block, lds, stream,
+                       (const T*)x, w, bias, (T*)y, row_mean, g);
+    MTR_CHECK_LAUNCH();
+    return MTR_OK;
+  });
 }
 
 }  // namespace mtr

@@ -212,19 +212,12 @@ static int launch_depthwise5x5(const void* x, const float* w, const float* bias,
   int blocks = g.n_groups < 256 * per_cu ? g.n_groups : 256 * per_cu;
   const dim3 grid((unsigned)blocks), block((unsigned)threads);
   MTR_CLEAR_STALE();
-#define MTR_DW5_LAUNCH(A)                                                                              \
-  hipLaunchKernelGGL((depthwise5x5_kernel<T, A, STRIDE>), grid, block, lds, stream, (const T*)x, w, bias, \
-                     (T*)y, row_mean, g, vec ? 1 : 0)
-  switch (act) {
-    case kActNone: MTR_DW5_LAUNCH(kActNone); break;
-    case kActRelu: MTR_DW5_LAUNCH(kActRelu); break;
-    case kActSilu: MTR_DW5_LAUNCH(kActSilu); break;
-    case kActHardswish: MTR_DW5_LAUNCH(kActHardswish); break;
-    default: return MTR_E_PARAM;
-  }
-#undef MTR_DW5_LAUNCH
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return dispatch_act(act, [&](auto tag) -> int {
+    hipLaunchKernelGGL((depthwise5x5_kernel<T, decltype(tag)::value, STRIDE>), grid, block, lds, stream, (const T*)x,
+                       w, bias, (T*)y, row_mean, g, vec ? 1 : 0);
+    MTR_CHECK_LAUNCH();
+    return MTR_OK;
+  });
 }
 
 template <typename T>

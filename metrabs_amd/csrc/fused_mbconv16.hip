@@ -51,8 +51,6 @@ template <> struct FmbBits<MTR_BF16> {
   }
 };
 
-template <int V> struct FmbActTag { static constexpr int value = V; };
-
 // the geometry of one launch, computed on the host (fmb_geometry) and used by both sides
 struct FmbGeo {
   int Cin, Cmid, Cout, H, W, Ho, Wo, stride;
@@ -259,11 +257,13 @@ __global__ __launch_bounds__(256) void fused_mbconv16_kernel(
         }
       }
     };
-    switch (act) {  // wave-uniform: one body per activation, the GEMMs shared
-      case kActRelu: to_image(FmbActTag<kActRelu>()); break;
-      case kActSilu: to_image(FmbActTag<kActSilu>()); break;
-      case kActHardswish: to_image(FmbActTag<kActHardswish>()); break;
-      default: to_image(FmbActTag<kActNone>()); break;
+    // wave-uniform: one body per activation, the GEMMs shared.  Written out: behind the shared with_act() a few
+    // instructions trade places inside the chunk loop
+    switch (act) {
+      case kActRelu: to_image(ActTag<kActRelu>()); break;
+      case kActSilu: to_image(ActTag<kActSilu>()); break;
+      case kActHardswish: to_image(ActTag<kActHardswish>()); break;
+      default: to_image(ActTag<kActNone>()); break;
     }
     __syncthreads();
 

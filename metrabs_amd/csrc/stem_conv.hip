@@ -67,8 +67,6 @@ template <> struct StemT<MTR_BF16> {
   }
 };
 
-template <int V> struct StemActTag { static constexpr int value = V; };
-
 // the geometry of one launch, computed on the host (stem_geometry) and used by both sides
 struct StemGeo {
   int M, H, W, Ho, Wo;
@@ -270,11 +268,13 @@ __global__ __launch_bounds__(kStemThreads) void stem_conv_kernel(
         __syncthreads();  // the rows are rewritten by the next channel tile / pass
       }
     };
-    switch (act) {  // wave-uniform
-      case kActRelu: epilogue(StemActTag<kActRelu>()); break;
-      case kActSilu: epilogue(StemActTag<kActSilu>()); break;
-      case kActHardswish: epilogue(StemActTag<kActHardswish>()); break;
-      default: epilogue(StemActTag<kActNone>()); break;
+    // wave-uniform.  Written out: behind the shared with_act() the f32 instantiations come out one instruction
+    // shorter, which is not the same code
+    switch (act) {
+      case kActRelu: epilogue(ActTag<kActRelu>()); break;
+      case kActSilu: epilogue(ActTag<kActSilu>()); break;
+      case kActHardswish: epilogue(ActTag<kActHardswish>()); break;
+      default: epilogue(ActTag<kActNone>()); break;
     }
   }
 }
