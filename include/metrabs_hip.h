@@ -733,6 +733,33 @@ int mtr_conv3x3_winograd_bias_act(const void* x, const float* weight_u /*[16][Co
  * input and of U), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_conv3x3_winograd_lds_bytes(long long B, int Cin, int Cout, int H, int W);
 
+/* K22 (outside the reference's hot path, like K10): a dense 3x3 convolution of f32 tensors -- STRIDE 2, padding 1 on
+ * all sides, no dilation, groups 1 -- as an implicit GEMM on the f32-input MFMA (v_mfma_f32_16x16x4_f32), with the K10
+ * epilogue folded in:
+ *   y[b, m, oy, ox] = act(bias[m] + sum_{ci, ky, kx} w[m, ci, ky, kx] * x[b, ci, 2 oy + ky - 1, 2 ox + kx - 1])
+ *                     (+ residual[b, m, oy, ox])
+ * x [B, Cin, H, W], y and residual [B, Cout, H / 2, W / 2]: f32, NCHW, contiguous, 16-byte aligned (else MTR_E_ALIGN).
+ * w_packed is the f32 OIHW weight PERMUTED (no arithmetic) to [Cin / 4][Cout][3][3][4]: element (c4, m, ky, kx, j) is
+ * w[m, 4 c4 + j, ky, kx]; contiguous, 16-byte aligned.  bias [Cout] f32; residual may be NULL; act_code as the `act`
+ * of mtr_bias_act_nchw, applied in K10's order (bias, activation, then the residual), else MTR_E_PARAM.
+ * Every output element is ONE chain of 9 Cin fmaf from 0, in the order: for c4 (chunks of four input channels), for
+ * ky, for kx, for ci = 4 c4 .. 4 c4 + 3: s = fmaf(x, w, s), padding taps entering as zeros -- the MFMA is bitwise such
+ * a chain.  MTR_E_SHAPE (the caller keeps the library path) unless Cin % 4 == 0, H and W are even, (W / 2) % 4 == 0,
+ * Cout >= 1, and Cin H W, Cout H W / 4, 9 Cin Cout and the grid are below 2^31; any Cout and B are taken.  A NULL x,
+ * w_packed, bias or y is MTR_E_NULL; y overlapping x or residual is MTR_E_PARAM.  Every check is made on the host
+ * before anything is enqueued; B == 0 returns MTR_OK without a launch.  No atomics, no split-K, no workspace, nothing
+ * allocated; only enqueues on `stream`: the same inputs give the same bits for any batch index and tile position, on
+ * every call and graph replay.  (The activation parameter is named act_code: tests/test_act_code_refusals.py keeps
+ * its own table of the declarations that say `int act`; this entry's refusals are pinned in
+ * tests/test_conv3x3_strided_host.py.) */
+int mtr_conv3x3s2_bias_act(const void* x, const float* w_packed /*[Cin/4][Cout][3][3][4]*/, const float* bias,
+                           const void* residual, int act_code, long long B, int Cin, int Cout, int H, int W, void* y,
+                           mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_conv3x3s2_bias_act uses for this shape (one chunk of the input halo and of the
+ * weight), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_conv3x3s2_lds_bytes(long long B, int Cin, int Cout, int H, int W);
+
 /* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
  * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
  *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32

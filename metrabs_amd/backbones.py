@@ -161,7 +161,7 @@ class FusedMBConv(nn.Module):
     # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
     # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
     fused_pair = ()
-    # 'k16h' / 'k13_pre' / 'k20_pre' / 'k19' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
+    # 'k16h' / 'k13_pre' / 'k20_pre' / 'k19' / 'k22' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
     # every other block
     last_path = None
     # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
@@ -204,7 +204,8 @@ class FusedMBConv(nn.Module):
         epilogue on K19, then the project and the skip as an ordinary call of the project layer -- K13, or K20 under
         split_gemm (the project's own last_path says which).  With K19 switched off or refusing, a
         WinogradConv3x3BiasAct in pre_pair[0] is the ConvBiasAct it derives from, and the block takes the other
-        branches.  'chain': what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
+        branches.  'k22' (fold_batchnorm(strided3x3=True)): the same for a stride-2 first layer, a
+        StridedConv3x3BiasAct, on K22.  'chain': what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
         nothing for them; the tensor without its epilogue goes to the project alone, which applies that epilogue on
         every path, and no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the
         branches with every option on.)"""
@@ -215,6 +216,10 @@ class FusedMBConv(nn.Module):
             # K19 applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
             # split_gemm; no prologue) with the skip
             self.last_path = 'k19'
+            return project(first(x), residual=residual)
+        if isinstance(first, StridedConv3x3BiasAct) and first.path(x) == 'k22':
+            # the same for a stride-2 expand: K22 with the layer's own epilogue, then the project as an ordinary call
+            self.last_path = 'k22'
             return project(first(x), residual=residual)
         self.last_path = 'chain'
         if not (FusedMBConv.use_k13_pre and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
@@ -823,6 +828,62 @@ class WinogradConv3x3BiasAct(ConvBiasAct):
         return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
 
 
+class StridedConv3x3BiasAct(ConvBiasAct):
+    """A folded dense 3x3, stride-2, padding-1 conv + BN (+ activation) with Cin % 4 == 0 of an f32 copy made with
+    fold_batchnorm(strided3x3=True): the convolution as an implicit GEMM on the f32 MFMA, "+ bias" and the activation
+    as ONE HIP launch (K22, conv3x3_strided.hip) instead of a MIOpen convolution followed by K10.  Same parameters and
+    state_dict keys as the ConvBiasAct it replaces (the packed weight is derived state, cached per weight storage and
+    version), which it also is for every input K22 does not take -- CPU, channels_last, autocast, a gradient wanted,
+    odd maps, the shapes listed as slower: those run exactly what ConvBiasAct runs."""
+
+    # class-wide switch (tests and A/B runs): the library path everywhere
+    use_k22 = True
+    # (Cin, Cout, H, W) of the input where K22 (for the expand of a FusedMBConv: K22 + the plain K13 project) was not
+    # ahead of the default copy's path in every round of tools/conv3x3_ab.py --dtype f32 (DESIGN.md section 28)
+    k22_slower = frozenset()
+
+    def __init__(self, conv, bias, act):
+        super().__init__(conv, bias, act)  # (last_path: 'k22' or 'library')
+        self._wsd = None
+
+    @staticmethod
+    def applies_to(conv):
+        return _dense_3x3(conv, strides=((2, 2),)) and conv.in_channels % 4 == 0
+
+    def weight_s(self):
+        """The conv's weight permuted for K22 ([Cin / 4, Cout, 3, 3, 4], kernels.pack_conv3x3_strided_weight): made on
+        the first K22 forward and kept as _derived_weight says."""
+        self._wsd = _derived_weight(self._wsd, self.conv.weight, kernels.pack_conv3x3_strided_weight)
+        return self._wsd[1]
+
+    def k22_takes(self, x):
+        """Whether forward(x) runs on K22: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
+        the C entry accepts and that is not listed as slower."""
+        c = self.conv
+        if not (StridedConv3x3BiasAct.use_k22 and not self.emit_mean and x.is_cuda and x.dim() == 4
+                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
+                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
+                and _inference_call(c.weight, x=x)):
+            return False
+        B, K, H, W = x.shape
+        if K != c.in_channels or (K, c.out_channels, H, W) in StridedConv3x3BiasAct.k22_slower:
+            return False
+        return _lib.load().mtr_conv3x3s2_lds_bytes(B, K, c.out_channels, H, W) > 0
+
+    def path(self, x, residual=None, pre=None, defer_epilogue=False):
+        """'k22' in front of ConvBiasAct's order (which, for a 3x3 layer, says 'library')."""
+        if not defer_epilogue and pre is None and self.k22_takes(x) and _addable(
+                residual, x, shape=(x.shape[0], self.conv.out_channels, x.shape[2] // 2, x.shape[3] // 2)):
+            return 'k22'
+        return super().path(x, residual, pre, defer_epilogue)
+
+    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
+        if self.path(x, residual, pre, defer_epilogue) == 'k22':
+            self.last_path = 'k22'
+            return kernels.conv3x3_strided_bias_act(x, self.weight_s(), self.bias, self.act_name, residual=residual)
+        return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+
+
 class DepthwiseBiasAct(nn.Module):
     """A folded depthwise 3x3 (K11) or 5x5 (K15) conv + BN + activation as ONE HIP pass over the plane: the
     convolution, "+ bias", the activation and -- in front of a squeeze-excite block -- the
@@ -1032,13 +1093,25 @@ def _replace_winograd(folded):
     _replace_conv_bias_act(folded, WinogradConv3x3BiasAct)
 
 
+def _replace_strided3x3(folded):
+    """strided3x3: every dense 3x3, stride-2, padding-1, ungrouped ConvBiasAct with Cin % 4 == 0 that emits no mean
+    becomes a StridedConv3x3BiasAct: 2 layers of EfficientNetV2-S, 2 of -L, 3 of ResNet-18, none of MobileNetV3 (the
+    stems have Cin = 3 and stay K17's).  Such a layer runs as an implicit GEMM on the f32 MFMA with "+ bias" and the
+    activation in one launch (K22, .last_path 'k22') where that kernel takes the input and the shape is not in
+    StridedConv3x3BiasAct.k22_slower, and exactly what ConvBiasAct runs everywhere else.  An armed FusedMBConv expand
+    block runs K22 with its own epilogue and then the project as a plain K13 call -- a plain K20 call with
+    split_gemm=True -- (block .last_path 'k22').  Results differ from the default copy's by rounding (another
+    summation order)."""
+    _replace_conv_bias_act(folded, StridedConv3x3BiasAct)
+
+
 def _arm_pre_pairs(folded):
     """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the WinogradConv3x3BiasAct
-    that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
+    or StridedConv3x3BiasAct that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
     and applied by the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with
     the bits of the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict."""
     for m in folded.modules():
-        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct))
+        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct, StridedConv3x3BiasAct))
         if pair:
             m.pre_pair = pair
 
@@ -1122,11 +1195,13 @@ _NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
           '16bit': (lambda fused, dtype: dtype is not None, 'a 16-bit copy (dtype=torch.float16 / torch.bfloat16)'),
           'f32': (lambda fused, dtype: fused and dtype is None, 'fused_epilogue=True and an f32 copy (no dtype=)')}
 _OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
-                 ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'))
+                 ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'),
+                 ('strided3x3', 'f32'))
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                   block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False):
+                   block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
+                   strided3x3=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -1149,12 +1224,15 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     winograd3x3=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype -- K14h serves the 16-bit copies): the
     dense 3x3 stride-1 layers as Winograd on the f32 MFMA, K19 (_replace_winograd).
     split_gemm=True (needs fused_epilogue=True and an f32 copy): the f32 1x1 layers on K20 (_arm_split_gemm).
-    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm; 16-bit:
+    strided3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-2 layers with Cin % 4 == 0 as an
+    implicit GEMM on the f32 MFMA, K22 (_replace_strided3x3).
+    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3; 16-bit:
     fuse_blocks, fuse_stem, block_depthwise, deep_projects): no two of them arm the same field of the same module, and
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
     module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
-    hand_to are taken after the replacements (WinogradConv3x3BiasAct, Conv3x3BiasAct, StemConvBiasAct); mean_from and
+    hand_to are taken after the replacements (WinogradConv3x3BiasAct, StridedConv3x3BiasAct, Conv3x3BiasAct,
+    StemConvBiasAct); mean_from and
     gate_to before them, at layers no replacement touches in these networks (those that emit a mean; the 1x1 projects).
     tests/test_backbone_option_combos_host.py checks every reference of every combination."""
     import copy
@@ -1165,7 +1243,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     if dtype is not None and not fused_epilogue:
         raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
     options = dict(fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
-                   deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm)
+                   deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
+                   strided3x3=strided3x3)
     for option, need in _OPTION_NEEDS:
         met, text = _NEEDS[need]
         if options[option] and not met(fused_epilogue, dtype):
@@ -1177,6 +1256,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         _wire_squeeze_excite(folded)
     if winograd3x3:
         _replace_winograd(folded)
+    if strided3x3:
+        _replace_strided3x3(folded)
     if fused_epilogue and dtype is None:
         _arm_pre_pairs(folded)
     if dtype is not None:

@@ -1113,6 +1113,68 @@ def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
     return out
 
 
+# K22: a dense 3x3 stride-2 convolution of f32 tensors as an implicit GEMM on the f32 MFMA, with the K10 epilogue
+# (csrc/conv3x3_strided.hip)
+
+def pack_conv3x3_strided_weight(weight):
+    """The [Cout, Cin, 3, 3] f32 convolution weight as mtr_conv3x3s2_bias_act takes it: a pure permutation to
+    [Cin / 4, Cout, 3, 3, 4], element (c4, m, ky, kx, j) = w[m, 4 c4 + j, ky, kx], contiguous -- the 36 floats one
+    output channel needs for a chunk of four input channels in one run, tap-major.  Plain torch; done once per weight."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] % 4:
+        raise ValueError(f'pack_conv3x3_strided_weight: expected [Cout, Cin, 3, 3] with Cin a multiple of 4, '
+                         f'got {tuple(weight.shape)}')
+    if weight.dtype != torch.float32:
+        raise ValueError(f'pack_conv3x3_strided_weight: expected an f32 weight, got {weight.dtype}')
+    M, K = weight.shape[:2]
+    return weight.detach().reshape(M, K // 4, 4, 3, 3).permute(1, 0, 3, 4, 2).contiguous()
+
+
+def conv3x3_strided_supported(x, w_packed):
+    """Whether mtr_conv3x3s2_bias_act takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
+    aligned, w_packed [Cin / 4, Cout, 3, 3, 4] f32 contiguous (pack_conv3x3_strided_weight), Cin a multiple of 4, H and
+    W even, W / 2 a multiple of 4 (its MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
+    if x.dim() != 4 or w_packed.dim() != 5 or x.dtype != torch.float32 or w_packed.dtype != torch.float32 \
+            or not x.is_cuda or not w_packed.is_cuda or not x.is_contiguous() or not w_packed.is_contiguous() \
+            or x.data_ptr() % 16 or w_packed.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if K % 4 or tuple(w_packed.shape[2:]) != (3, 3, 4) or w_packed.shape[0] != K // 4:
+        return False
+    return _lib.load().mtr_conv3x3s2_lds_bytes(B, K, w_packed.shape[1], H, W) > 0
+
+
+def conv3x3_strided_bias_act(x, w_packed, bias, act, residual=None, out=None):
+    """y = act(conv3x3(x, w, stride 2, padding 1) + bias) (+ residual) in one launch on the current stream, for f32:
+    x [B, Cin, H, W] NCHW-contiguous, w_packed [Cin / 4, Cout, 3, 3, 4] (pack_conv3x3_strided_weight), bias [Cout] f32,
+    residual [B, Cout, H / 2, W / 2] f32 or None.  One f32 fma chain per output element in a fixed order of (ci, ky,
+    kx): the same bits on every call and graph replay, for any batch size."""
+    require_cuda(x, w_packed, bias, residual)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('conv3x3_strided_bias_act: x must be [B, Cin, H, W], NCHW-contiguous')
+    if x.dtype != torch.float32 or w_packed.dtype != torch.float32:
+        raise ValueError(f'conv3x3_strided_bias_act: x and the weight must be f32, got {x.dtype} and {w_packed.dtype}')
+    B, K, H, W = x.shape
+    if w_packed.dim() != 5 or K % 4 or tuple(w_packed.shape[2:]) != (3, 3, 4) or w_packed.shape[0] != K // 4 \
+            or not w_packed.is_contiguous():
+        raise ValueError(f'conv3x3_strided_bias_act: the weight must be packed [{K} / 4, Cout, 3, 3, 4] and '
+                         f'contiguous, got {tuple(w_packed.shape)}')
+    M = w_packed.shape[1]
+    if bias.numel() != M:
+        raise ValueError(f'conv3x3_strided_bias_act: bias has {bias.numel()} elements, expected {M}')
+    if H % 2 or W % 2:
+        raise ValueError(f'conv3x3_strided_bias_act: H and W must be even, got {H} x {W}')
+    out = _residual_and_out('conv3x3_strided_bias_act', x, (B, M, H // 2, W // 2), residual, out,
+                            hw='H / 2, W / 2')
+    for t, name in ((x, 'x'), (residual, 'residual')):
+        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
+                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError(f'conv3x3_strided_bias_act: out must not overlap {name}')
+    check(_lib.load().mtr_conv3x3s2_bias_act(
+        _ptr(x), _ptr(w_packed), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3s2_bias_act')
+    return out
+
+
 # K20: a 1x1 stride-1 convolution of f32 tensors on the bf16 matrix cores, from operands split into three bf16 pieces
 # (csrc/conv1x1_split.hip)
 

@@ -56,7 +56,7 @@ def load_joint_info(model_dir):
 
 def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
                     fuse_blocks=False, fuse_stem=False, block_depthwise=False, deep_projects=False,
-                    winograd3x3=False, split_gemm=False):
+                    winograd3x3=False, split_gemm=False, strided3x3=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
@@ -82,7 +82,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     split_gemm=True (an f32 copy only, else ValueError; off by default; independent of the other options) runs the
     copy's 1x1 stride-1 convolutions on the bf16 matrix cores from operands split into three bf16 pieces
     (backbones.fold_batchnorm(split_gemm=True), K20): f32-grade, equal to the default copy up to rounding.  Like
-    fuse_stem it always gives the folded copy with fused epilogues."""
+    fuse_stem it always gives the folded copy with fused epilogues.
+    strided3x3=True (an f32 copy only, else ValueError; off by default; independent of the other options) runs the
+    copy's dense 3x3 stride-2 layers with Cin % 4 == 0 as an implicit GEMM on the f32 MFMA with their epilogue folded in
+    (backbones.fold_batchnorm(strided3x3=True), K22): equal to the default copy up to rounding.  Like fuse_stem it
+    always gives the folded copy with fused epilogues."""
     if dtype == torch.float32:
         dtype = None
     if dtype not in (None, torch.float16, torch.bfloat16):
@@ -96,6 +100,8 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
         raise ValueError('load_crop_model: winograd3x3=True needs an f32 copy (dtype=None or torch.float32)')
     if split_gemm and dtype is not None:
         raise ValueError('load_crop_model: split_gemm=True needs an f32 copy (dtype=None or torch.float32)')
+    if strided3x3 and dtype is not None:
+        raise ValueError('load_crop_model: strided3x3=True needs an f32 copy (dtype=None or torch.float32)')
     cfg, raw = load_config(model_dir)
     # config.affine_weights (models/metrabs.py:23-32) is a path or a name under $DATA_ROOT/skeleton_conversion;
     # a file of that name shipped INSIDE the model directory is found too
@@ -115,10 +121,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, dtype=dtype, fuse_blocks=fuse_blocks,
                               fuse_stem=fuse_stem, block_depthwise=block_depthwise, deep_projects=deep_projects)
-    elif fuse_stem or block_depthwise or winograd3x3 or split_gemm:
+    elif fuse_stem or block_depthwise or winograd3x3 or split_gemm or strided3x3:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=fuse_stem,
-                              block_depthwise=block_depthwise, winograd3x3=winograd3x3, split_gemm=split_gemm)
+                              block_depthwise=block_depthwise, winograd3x3=winograd3x3, split_gemm=split_gemm,
+                              strided3x3=strided3x3)
     elif fold_batchnorm:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=fused_epilogue)
@@ -127,13 +134,15 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
 
 def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchnorm=False,
                            fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
-                           block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False):
+                           block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
+                           strided3x3=False):
     """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise, deep_projects,
-    winograd3x3, split_gemm:
+    winograd3x3, split_gemm, strided3x3:
     as load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
     model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
                             fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
-                            deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm)
+                            deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
+                            strided3x3=strided3x3)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

@@ -34,6 +34,10 @@ arms differ by rounding; the rows carry ab='k19' and the paths of the armed laye
 split_gemm=True (the 1x1 stride-1 layers on K20, the split-operand kernel, where ConvBiasAct.k20_slower does not list
 them); --winograd3x3 folds BOTH arms with winograd3x3=True as well.  The arms differ by rounding; the rows carry
 ab='k20' and the paths of the 1x1 layers of both arms.
+--ab k22: both arms are the f32 copy of the same network (--dtype f32; --config 1), A folded as by default, B with
+strided3x3=True (the dense 3x3 stride-2 layers on K22 where StridedConv3x3BiasAct.k22_slower does not list them);
+--winograd3x3 folds BOTH arms with winograd3x3=True as well.  The arms differ by rounding; the rows carry ab='k22', the
+paths of the armed layers and the MPJPE between the two arms' poses.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -53,21 +57,24 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20'], default='copy',
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22'],
+                    default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
                          "k18: without vs with block_depthwise; deepk: without vs with deep_projects; "
                          "k19 (--dtype f32): the f32 copy folded without vs with winograd3x3; "
-                         "k20 (--dtype f32): the f32 copy folded without vs with split_gemm")
-    ap.add_argument('--winograd3x3', action='store_true', help='--ab k20: fold both arms with winograd3x3=True too')
+                         "k20 (--dtype f32): the f32 copy folded without vs with split_gemm; "
+                         "k22 (--dtype f32): the f32 copy folded without vs with strided3x3")
+    ap.add_argument('--winograd3x3', action='store_true',
+                    help='--ab k20, --ab k22: fold both arms with winograd3x3=True too')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19', 'k20'):
-        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18, --ab k19 or --ab k20')
-    if args.ab in ('k19', 'k20') and args.dtype != 'f32':
+    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19', 'k20', 'k22'):
+        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18, --ab k19, --ab k20 or --ab k22')
+    if args.ab in ('k19', 'k20', 'k22') and args.dtype != 'f32':
         ap.error(f'--ab {args.ab} goes with --dtype f32')
-    if args.winograd3x3 and args.ab != 'k20':
-        ap.error('--winograd3x3 goes with --ab k20')
+    if args.winograd3x3 and args.ab not in ('k20', 'k22'):
+        ap.error('--winograd3x3 goes with --ab k20 or --ab k22')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -126,6 +133,16 @@ def main():
             e.crop_dtype = e.crop_model.input_dtype
             e.crop_model.autocast_dtype = None                   # f32 copies, run in f32
         assert any(isinstance(m, ConvBiasAct) and m.split_gemm for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k22':                                         # both arms the f32 copy, B with K22 armed
+        from metrabs_amd.backbones import StridedConv3x3BiasAct
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True,
+                                                   winograd3x3=args.winograd3x3)
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True,
+                                                   winograd3x3=args.winograd3x3, strided3x3=True)
+        for e in (est_a, est_b):
+            e.crop_dtype = e.crop_model.input_dtype
+            e.crop_model.autocast_dtype = None                   # f32 copies, run in f32
+        assert any(isinstance(m, StridedConv3x3BiasAct) for m in est_b.crop_model.backbone.modules())
     if args.ab == 'deepk':                                       # both arms the 16-bit copy, B with its deep projects armed
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -232,6 +249,14 @@ def main():
                    mpjpe_armed_vs_default_mm=round(float((p_b - p_a).norm(dim=-1).mean()), 5),
                    a={str(k): paths[0].count(k) for k in sorted(set(paths[0]), key=str)},
                    b={str(k): paths[1].count(k) for k in sorted(set(paths[1]), key=str)})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k22':
+        from metrabs_amd.backbones import StridedConv3x3BiasAct
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules() if isinstance(m, StridedConv3x3BiasAct)]
+        row = dict(kind='paths', ab='k22', winograd3x3=args.winograd3x3,
+                   mpjpe_armed_vs_default_mm=round(float((p_b - p_a).norm(dim=-1).mean()), 5),
+                   b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
         print(json.dumps(row), flush=True)
         rows.append(row)
     if args.ab == 'deepk':

@@ -21,6 +21,10 @@ of a FusedMBConv block (stages 2 - 3) is timed as the PAIR, because the prologue
 MIOpen convolution + K13 with the prologue against K19 + the plain K13 call.  Every record carries the per-round times
 of both arms, the share of the 155 TF f32 matrix peak counted in Winograd-domain FLOP (16 products per 2x2 tile and
 channel pair; the pair's project not counted) and the share of the byte floor of the 3x3 layer.
+The stride-2 classes of the copy folded with strided3x3=True are timed in the same run, K22
+(kernels.conv3x3_strided_bias_act) in the place of K19: a FusedMBConv expand as the pair (MIOpen pinned + K13 with the
+prologue against K22 + the plain K13 call), a ResNet layer alone against MIOpen + K10; their records say stride 2 and
+k22_*, and the share of the matrix peak is counted in direct-convolution FLOP.
 """
 import argparse
 import json
@@ -52,12 +56,13 @@ def shape_classes(res, backbone, dtype):
 
 
 def shape_classes_f32(res, backbone):
-    """(Cin, Cout, H, W, act, skip, project Cout or None) -> module names, from a hooked forward of the armed copy."""
+    """(Cin, Cout, H, W, act, skip, project Cout or None, stride) -> module names, from a hooked forward of the copy armed
+    with winograd3x3 (the stride-1 classes, K19) and strided3x3 (the stride-2 classes, K22)."""
     import torch
     from metrabs_amd import backbones
-    W3 = backbones.WinogradConv3x3BiasAct
+    W3 = (backbones.WinogradConv3x3BiasAct, backbones.StridedConv3x3BiasAct)
     net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True,
-                                   winograd3x3=True).cuda()
+                                   winograd3x3=True, strided3x3=True).cuda()
     out, paired = {}, set()
     for name, m in net.named_modules():
         if isinstance(m, backbones.FusedMBConv) and m.pre_pair and isinstance(m.pre_pair[0], W3):
@@ -66,7 +71,7 @@ def shape_classes_f32(res, backbone):
             def hook(mod, args, name=name):
                 x, (first, project) = args[0], mod.pre_pair
                 key = (x.shape[1], first.conv.out_channels, x.shape[2], x.shape[3], first.act_name, mod.residual,
-                       project.conv.out_channels)
+                       project.conv.out_channels, first.conv.stride[0])
                 out.setdefault(key, []).append(name)
             m.register_forward_pre_hook(hook)
     for name, m in net.named_modules():
@@ -74,15 +79,15 @@ def shape_classes_f32(res, backbone):
             def hook(mod, args, kwargs, name=name):
                 x = args[0]
                 key = (x.shape[1], mod.conv.out_channels, x.shape[2], x.shape[3], mod.act_name,
-                       kwargs.get('residual') is not None, None)
+                       kwargs.get('residual') is not None, None, mod.conv.stride[0])
                 out.setdefault(key, []).append(name)
             m.register_forward_pre_hook(hook, with_kwargs=True)
-    W3.use_k19 = False
+    W3[0].use_k19 = W3[1].use_k22 = False
     try:
         with torch.inference_mode():
             net(torch.rand(1, 3, res, res, device='cuda'))
     finally:
-        W3.use_k19 = True
+        W3[0].use_k19 = W3[1].use_k22 = True
     return out
 
 
@@ -95,34 +100,41 @@ def main_f32(args):
     g = torch.Generator(device='cuda').manual_seed(0)
     B = args.batch
     med = lambda v: sorted(v)[len(v) // 2]
-    for (K, M, H, W, act, skip, P), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+    for (K, M, H, W, act, skip, P, stride), names in sorted(classes.items(), key=lambda kv: kv[1][0]):
+        # tag: the kernel of the new arm, K19 for the stride-1 classes and K22 for the stride-2 ones
+        tag, pack, takes, conv = {
+            1: ('k19', kernels.pack_conv3x3_winograd_weight, kernels.conv3x3_winograd_supported,
+                kernels.conv3x3_winograd_bias_act),
+            2: ('k22', kernels.pack_conv3x3_strided_weight, kernels.conv3x3_strided_supported,
+                kernels.conv3x3_strided_bias_act)}[stride]
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         x = torch.randn(B, K, H, W, device='cuda', generator=g)
         w = torch.randn(M, K, 3, 3, device='cuda', generator=g) / (9 * K) ** 0.5
-        wu = kernels.pack_conv3x3_winograd_weight(w)
+        wu = pack(w)
         b = torch.randn(M, device='cuda', generator=g)
-        y = torch.empty(B, M, H, W, device='cuda')
-        supported = kernels.conv3x3_winograd_supported(x, wu)
+        y = torch.empty(B, M, Ho, Wo, device='cuda')
+        supported = takes(x, wu)
         if P is None:
-            r = torch.randn(B, M, H, W, device='cuda', generator=g) if skip else None
+            r = torch.randn(B, M, Ho, Wo, device='cuda', generator=g) if skip else None
 
             def old():
-                yy = F.conv2d(x, w, None, 1, 1)
+                yy = F.conv2d(x, w, None, stride, 1)
                 kernels.bias_act_(yy, b, act, r)
                 return yy
 
             def new():
-                return kernels.conv3x3_winograd_bias_act(x, wu, b, act, residual=r, out=y)
+                return conv(x, wu, b, act, residual=r, out=y)
         else:
             w1 = torch.randn(P, M, 1, 1, device='cuda', generator=g) / M ** 0.5
             b1 = torch.randn(P, device='cuda', generator=g)
-            r = torch.randn(B, P, H, W, device='cuda', generator=g) if skip else None
+            r = torch.randn(B, P, Ho, Wo, device='cuda', generator=g) if skip else None
 
             def old():
-                return kernels.conv1x1_bias_act(F.conv2d(x, w, None, 1, 1), w1, b1, None, residual=r, in_bias=b,
+                return kernels.conv1x1_bias_act(F.conv2d(x, w, None, stride, 1), w1, b1, None, residual=r, in_bias=b,
                                                 in_act=act)
 
             def new():
-                kernels.conv3x3_winograd_bias_act(x, wu, b, act, out=y)
+                conv(x, wu, b, act, out=y)
                 return kernels.conv1x1_bias_act(y, w1, b1, None, residual=r)
 
         def captured(fn):
@@ -170,23 +182,25 @@ def main_f32(args):
                 if supported:
                     t_new.append(timed(arm_new))
             del arm_old, arm_new
-        wino_flop = 2.0 * B * (H // 2) * (W // 2) * 16 * K * M
-        byts = 4 * (B * H * W * (K + M * (2 if (skip and P is None) else 1)) + 16 * M * K)
+        direct_flop = 2.0 * B * Ho * Wo * 9 * K * M
+        # what the new arm's MFMAs compute: the Winograd-domain products of K19, the direct convolution of K22
+        wino_flop = 2.0 * B * (H // 2) * (W // 2) * 16 * K * M if stride == 1 else direct_flop
+        byts = 4 * (B * (H * W * K + Ho * Wo * M * (2 if (skip and P is None) else 1)) + (16 if stride == 1 else 9) * M * K)
         byte_floor = byts / (HBM_TBS * 1e12) * 1e6
-        row = dict(cin=K, cout=M, hw=f'{H}x{W}', act=act, skip=skip, project_cout=P,
+        row = dict(cin=K, cout=M, hw=f'{H}x{W}', stride=stride, act=act, skip=skip, project_cout=P,
                    timed='pair with the K13 project' if P is not None else 'layer', layers=len(names), first=names[0],
                    dtype='f32', batch=B, res=args.res, backbone=args.backbone,
-                   direct_gflop=round(2.0 * B * H * W * 9 * K * M / 1e9, 2), winograd_gflop=round(wino_flop / 1e9, 2),
+                   direct_gflop=round(direct_flop / 1e9, 2), winograd_gflop=round(wino_flop / 1e9, 2) if stride == 1 else None,
                    mbytes=round(byts / 1e6, 1), old_us=round(med(t_old), 2), old_us_rounds=[round(t, 2) for t in t_old],
-                   k19_us=None)
+                   **{tag + '_us': None})
         if supported:
             t = med(t_new)
-            row.update(k19_us=round(t, 2), k19_us_rounds=[round(v, 2) for v in t_new],
-                       speedup=round(med(t_old) / t, 3), k19_ahead_in_every_round=max(t_new) < min(t_old),
-                       rel_diff=diff, byte_floor_us=round(byte_floor, 2))
+            row.update({tag + '_us': round(t, 2), tag + '_us_rounds': [round(v, 2) for v in t_new],
+                        tag + '_ahead_in_every_round': max(t_new) < min(t_old)},
+                       speedup=round(med(t_old) / t, 3), rel_diff=diff, byte_floor_us=round(byte_floor, 2))
             if P is None:   # (of a pair only the sum is timed: no share for the 3x3 layer alone)
-                row.update(k19_winograd_tflops=round(wino_flop / t / 1e6, 1),
-                           k19_share_of_f32_peak=round(wino_flop / t / 1e6 / PEAK32_TF, 3),
+                row.update({tag + ('_winograd_tflops' if stride == 1 else '_direct_tflops'): round(wino_flop / t / 1e6, 1),
+                            tag + '_share_of_f32_peak': round(wino_flop / t / 1e6 / PEAK32_TF, 3)},
                            share_of_byte_floor=round(byte_floor / t, 3))
         rows.append(row)
         print(json.dumps(row), flush=True)
