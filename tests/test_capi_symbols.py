@@ -46,6 +46,120 @@ def test_struct_layouts_match_header():
     assert int(re.search(r'#define MTR_WARP_PARAM_FLOATS (\d+)', text).group(1)) == _lib.MTR_WARP_PARAM_FLOATS
 
 
+def _header_without_comments():
+    return re.sub(r'/\*.*?\*/', ' ', open(HEADER).read(), flags=re.S)
+
+
+def _c_kind(decl):
+    """One parameter (or return type) of a prototype -> 'ptr', 'int', 'long long', 'size_t', 'float' or 'double'."""
+    decl = ' '.join(decl.split())
+    if '*' in decl or re.search(r'\bmtr_stream_t\b', decl):
+        return 'ptr'
+    words = [w for w in re.findall(r'[A-Za-z_]\w*', decl) if w not in ('const', 'unsigned', 'signed')]
+    for kind in ('long long', 'size_t', 'float', 'double', 'int'):
+        if words[:len(kind.split())] == kind.split():
+            return kind
+    raise AssertionError(f'unknown parameter type in the header: {decl!r}')
+
+
+def declared_prototypes():
+    """name -> (return kind, [argument kinds]) of every function include/metrabs_hip.h declares."""
+    protos = {}
+    for m in re.finditer(r'^\s*(int|size_t|const char\s*\*)\s*(mtr_\w+)\s*\(([^;{]*?)\)\s*;',
+                         _header_without_comments(), flags=re.M | re.S):
+        ret, name, args = m.groups()
+        args = args.strip()
+        kinds = [] if args in ('', 'void') else [_c_kind(a) for a in args.split(',')]
+        protos[name] = (_c_kind(ret), kinds)
+    return protos
+
+
+def _ctypes_kind(t):
+    if t is int:   # (mtr_conv1x1_split_supported: the C int read into Python's int, see _lib.SIGNATURES)
+        return 'int'
+    scalars = {ctypes.c_int: 'int', ctypes.c_longlong: 'long long', ctypes.c_size_t: 'size_t',
+               ctypes.c_float: 'float', ctypes.c_double: 'double'}
+    assert len(scalars) == 5   # no two of them are one ctypes class on this platform
+    if t in scalars:
+        return scalars[t]
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return 'ptr'
+    raise AssertionError(f'unknown ctypes type in _lib.SIGNATURES: {t!r}')
+
+
+def test_the_prototype_parser_reads_what_it_is_given():
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions()
+    assert protos['mtr_version'] == ('int', []) and protos['mtr_strerror'] == ('ptr', ['int'])
+    assert protos['mtr_head_packed_bytes'] == ('size_t', ['int'] * 4)
+    assert protos['mtr_conv1x1_plan'] == ('int', ['int', 'int', 'int', 'long long', 'int', 'ptr'])
+    assert _c_kind('const mtr_detector_geom* g') == 'ptr' and _c_kind('mtr_stream_t stream') == 'ptr'
+    assert _c_kind('long long B') == 'long long' and _c_kind('size_t workspace_bytes') == 'size_t'
+    assert _ctypes_kind(ctypes.POINTER(ctypes.c_int32)) == 'ptr' and _ctypes_kind(ctypes.c_longlong) == 'long long'
+
+
+def test_ctypes_argument_lists_match_the_header():
+    """Count and kind (pointer / stream, int, long long, size_t, float, double) of every argument, and the return
+    type: a `long long B` bound as c_int in the middle of 17 arguments shifts nothing on x86-64 and reads garbage."""
+    from metrabs_amd import _lib
+    protos = declared_prototypes()
+    assert sorted(protos) == sorted(_lib.SIGNATURES)
+    for name, (restype, argtypes) in sorted(_lib.SIGNATURES.items()):
+        ret, kinds = protos[name]
+        assert _ctypes_kind(restype) == ret, (name, restype, ret)
+        assert [_ctypes_kind(a) for a in argtypes] == kinds, (name, [_ctypes_kind(a) for a in argtypes], kinds)
+
+
+STRUCTS = {'mtr_head_params': 'HeadParams', 'mtr_head_options': 'HeadOptions', 'mtr_head_plan_info': 'HeadPlanInfo',
+           'mtr_recon_params': 'ReconParams', 'mtr_detector_geom': 'DetectorGeom', 'mtr_filter_params': 'FilterParams'}
+
+
+def header_struct_fields():
+    """struct name -> its field names in order, for every struct include/metrabs_hip.h defines."""
+    structs = {}
+    for m in re.finditer(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;', _header_without_comments(), flags=re.S):
+        assert m.group(1) == m.group(3)
+        names = []
+        for decl in m.group(2).split(';'):
+            if decl.strip():
+                first, *rest = decl.split(',')
+                names += [first.split()[-1]] + [r.strip() for r in rest]
+        structs[m.group(1)] = names
+    return structs
+
+
+def test_every_struct_layout_matches_the_header(tmp_path):
+    """sizeof and every offsetof, as the host C compiler lays the header's six structs out, against the ctypes classes."""
+    import shutil
+    import subprocess
+    from metrabs_amd import _lib
+    fields = header_struct_fields()
+    assert sorted(fields) == sorted(STRUCTS)
+    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang') if c and shutil.which(c)), None)
+    assert cc, 'no host C compiler'
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "metrabs_hip.h"', 'int main(void) {']
+    for s, names in sorted(fields.items()):
+        lines.append(f'  printf("{s} sizeof %zu\\n", sizeof({s}));')
+        for f in names:
+            lines.append(f'  printf("{s} {f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));')
+    lines += ['  return 0;', '}']
+    src, exe = tmp_path / 'layout.c', tmp_path / 'layout'
+    src.write_text('\n'.join(lines) + '\n')
+    subprocess.run([cc, '-std=c99', '-I', os.path.dirname(HEADER), str(src), '-o', str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split('\n')
+    seen = {s: [] for s in fields}
+    for s, f, *nums in (l.split() for l in out if l):
+        cls = getattr(_lib, STRUCTS[s])
+        if f == 'sizeof':
+            assert ctypes.sizeof(cls) == int(nums[0]), (s, ctypes.sizeof(cls), nums)
+        else:
+            d = getattr(cls, f)
+            assert (d.offset, d.size) == (int(nums[0]), int(nums[1])), (s, f, d.offset, d.size, nums)
+            seen[s].append(f)
+    for s, names in fields.items():
+        assert seen[s] == names == [n for n, _ in getattr(_lib, STRUCTS[s])._fields_], s
+
+
 def test_version_strerror_and_host_side_argument_checks(lib):
     from metrabs_amd import _lib
     assert lib.mtr_version() == 100

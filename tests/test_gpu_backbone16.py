@@ -51,8 +51,8 @@ def _inputs(B, K, M, H, W, seed, gate, residual, dtype):
     return x, w, b, gt, r
 
 
-def _check(x, w, b, act, gt, r, got):
-    """|got - fp64| <= one unit in the last place of the 16-bit result + an f32-accumulation term
+def _reference(x, w, b, act, gt, r):
+    """(fp64 result, bound): |got - fp64| <= one unit in the last place of the 16-bit result + an f32-accumulation term
     ~ K 2^-24 sum_k |w xg| (through the activation, Lipschitz <= 1.1 here), where xg is torch's x * gate.to(x.dtype)
     and the fp64 sum runs over the 16-bit operands."""
     dt = x.dtype
@@ -66,8 +66,13 @@ def _check(x, w, b, act, gt, r, got):
         ref = ref + r.double()
     tiny = torch.finfo(dt).tiny
     ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp_min(tiny))) - _MANT[dt])
-    bound = ulp + 1.1 * K * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24
-    assert got.shape == ref.shape and got.dtype == dt
+    return ref, ulp + 1.1 * K * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24
+
+
+def _check(x, w, b, act, gt, r, got):
+    """_reference's bound on every element (tests/conv_fuzz.py uses the same two functions)."""
+    ref, bound = _reference(x, w, b, act, gt, r)
+    assert got.shape == ref.shape and got.dtype == x.dtype
     excess = float(((got.double() - ref).abs() - bound).max())
     assert excess <= 0, excess
 

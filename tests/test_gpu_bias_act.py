@@ -52,6 +52,19 @@ def _inputs(shape, dtype, seed, residual=False):
     return y, b, r
 
 
+def _ref_and_bound(y, b, r, act):
+    """(fp64 result, the bound of the module docstring) of the input y (of the tensor's dtype), bias and skip."""
+    uo, tiny = U_OUT[y.dtype], TINY[y.dtype]
+    yd, bd = y.double(), b.double().view(1, -1, 1, 1)
+    t = yd + bd
+    ref = _act64(t, act)
+    E = 1.5 * U * (yd.abs() + bd.abs()) + (8 + 2 * t.abs()) * U * ref.abs()
+    if r is not None:
+        ref = ref + r.double()
+        E = E * (1 + U) + U * ref.abs()
+    return ref, E * (1 + uo) + uo * ref.abs() + tiny
+
+
 def _check(y, b, r, act, got, mean=None, tag=''):
     """got (and the row mean of got) against the fp64 bound, in slices of the batch of at most 2^22 elements.
     Returns (largest share of the bound, largest share of the mean's bound)."""
@@ -61,14 +74,7 @@ def _check(y, b, r, act, got, mean=None, tag=''):
     step = max(1, (1 << 22) // max(1, y[0].numel()))
     share = mshare = 0.0
     for i in range(0, B, step):
-        yd, bd = y[i:i + step].double(), b.double().view(1, -1, 1, 1)
-        t = yd + bd
-        ref = _act64(t, act)
-        E = 1.5 * U * (yd.abs() + bd.abs()) + (8 + 2 * t.abs()) * U * ref.abs()
-        if r is not None:
-            ref = ref + r[i:i + step].double()
-            E = E * (1 + U) + U * ref.abs()
-        bound = E * (1 + uo) + uo * ref.abs() + tiny
+        ref, bound = _ref_and_bound(y[i:i + step], b, None if r is None else r[i:i + step], act)
         gd = got[i:i + step].double()
         share = max(share, float(((gd - ref).abs() / bound).max()))
         if mean is not None:

@@ -44,9 +44,9 @@ def _inputs(B, K, M, H, W, seed, gate, residual):
     return x, w, b, gt, r
 
 
-def _check(x, w, b, act, gt, r, got):
-    """|got - fp64| <= a small multiple of 2^-23 * sum_k |w x| (the f32 MFMA is an fmaf chain), through
-    the activation (Lipschitz <= 1.1 for every act here) plus its own f32 rounding."""
+def _reference(x, w, b, act, gt, r):
+    """(fp64 result, bound): |got - fp64| <= a small multiple of 2^-23 * sum_k |w x| (the f32 MFMA is an fmaf chain),
+    through the activation (Lipschitz <= 1.1 for every act here) plus its own f32 rounding."""
     xg = x if gt is None else x * gt[:, :, None, None]        # f32, rounded as torch's x * g
     wd = w.double().flatten(1)
     z = torch.einsum('mk,bkhw->bmhw', wd, xg.double()) + b.double()[None, :, None, None]
@@ -54,7 +54,12 @@ def _check(x, w, b, act, gt, r, got):
     ref = _TORCH_ACT[act](z)
     if r is not None:
         ref = ref + r.double()
-    bound = 4 * 2.0 ** -23 * 1.1 * s + 1e-6 * ref.abs() + 1e-30
+    return ref, 4 * 2.0 ** -23 * 1.1 * s + 1e-6 * ref.abs() + 1e-30
+
+
+def _check(x, w, b, act, gt, r, got):
+    """_reference's bound on every element (tests/conv_fuzz.py uses the same two functions)."""
+    ref, bound = _reference(x, w, b, act, gt, r)
     assert got.shape == ref.shape and got.dtype == torch.float32
     excess = float(((got.double() - ref).abs() - bound).max())
     assert excess <= 0, excess

@@ -63,10 +63,10 @@ def _inputs(B, K, M, H, W, stride, seed, residual, dtype, border=1.0):
     return x, w, b, r
 
 
-def _check(x, w, b, act, stride, r, got):
-    """test_gpu_backbone16._check with K = 9 Cin: |got - fp64| <= one unit in the last place of the 16-bit result +
-    1.1 K 2^-24 sum |w| |x| (f32 accumulation through the activation, Lipschitz <= 1.1) + 1e-6 |ref| + 2^-24.
-    The fp64 reference is F.conv2d on the 16-bit operands cast to double; every element is checked."""
+def _reference(x, w, b, act, stride, r):
+    """(fp64 result, bound).  test_gpu_backbone16._check with K = 9 Cin: |got - fp64| <= one unit in the last place of
+    the 16-bit result + 1.1 K 2^-24 sum |w| |x| (f32 accumulation through the activation, Lipschitz <= 1.1) +
+    1e-6 |ref| + 2^-24.  The fp64 reference is F.conv2d on the 16-bit operands cast to double."""
     dt = x.dtype
     K = 9 * x.shape[1]
     z = F.conv2d(x.double(), w.double(), None, stride, 1) + b.double()[None, :, None, None]
@@ -76,7 +76,13 @@ def _check(x, w, b, act, stride, r, got):
         ref = ref + r.double()
     tiny = torch.finfo(dt).tiny
     ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp_min(tiny))) - _MANT[dt])
-    bound = ulp + 1.1 * K * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24
+    return ref, ulp + 1.1 * K * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24
+
+
+def _check(x, w, b, act, stride, r, got):
+    """_reference's bound on every element (tests/conv_fuzz.py uses the same two functions)."""
+    dt = x.dtype
+    ref, bound = _reference(x, w, b, act, stride, r)
     assert got.shape == ref.shape and got.dtype == dt
     err = (got.double() - ref).abs()
     print(f'k14h check {tuple(x.shape)} -> {tuple(got.shape)} s{stride} {act} {dt}: '

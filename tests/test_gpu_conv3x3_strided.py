@@ -49,12 +49,17 @@ def _ref64(x, w, b, act, r):
     return ref if r is None else ref + r.double()
 
 
-def _check(x, w, b, act, r, got):
-    """The bound of the module docstring, on every element."""
+def _reference(x, w, b, act, r):
+    """(fp64 result, the bound of the module docstring)."""
     K = x.shape[1]
     ref = _ref64(x, w, b, act, r)
     S = F.conv2d(x.double().abs(), w.double().abs(), None, 2, 1) + b.double().abs()[None, :, None, None]
-    bound = 1.1 * (9 * K + 2) * 2.0 ** -24 * S + 1e-6 * ref.abs() + 2.0 ** -24
+    return ref, 1.1 * (9 * K + 2) * 2.0 ** -24 * S + 1e-6 * ref.abs() + 2.0 ** -24
+
+
+def _check(x, w, b, act, r, got):
+    """The bound of the module docstring, on every element (tests/conv_fuzz.py uses the same two functions)."""
+    ref, bound = _reference(x, w, b, act, r)
     assert got.shape == ref.shape and got.dtype == torch.float32
     err = (got.double() - ref).abs()
     print(f'k22 check {tuple(x.shape)} -> {tuple(got.shape)} {act} skip {r is not None}: '

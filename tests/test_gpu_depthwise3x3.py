@@ -229,6 +229,19 @@ def _ordered(t):
     return torch.where(i < 0, -(i & 0x7fff), i)
 
 
+def _bound(v, S, ref, dtype):
+    """The bound of the module docstring from the fp64 pre-activation v, S = sum |x w| + |b| and ref = act(v)."""
+    E = 1.5 * 11 * U * S + (8 + 2 * v.abs()) * U * ref.abs()
+    return E * (1 + U_OUT[dtype]) + U_OUT[dtype] * ref.abs() + TINY[dtype]
+
+
+def _ref_and_bound(x, w, b, act, stride, pad):
+    """(fp64 result, bound) of a whole (small) case: what _check compares every y with (tests/conv_fuzz.py)."""
+    v, S = _conv64(x, w, b, stride, pad)
+    ref = _act64(v, act)
+    return ref, _bound(v, S, ref, x.dtype)
+
+
 def _check(x, w, b, act, stride, pad, outs, tag='', spread=None):
     """Every (y, mean) of outs against the fp64 bound; the reference is formed once, in slices of the batch of at most
     2^22 outputs (the fp64 temporaries of the largest cases stay small).  Returns the largest shares of the two bounds.
@@ -243,8 +256,7 @@ def _check(x, w, b, act, stride, pad, outs, tag='', spread=None):
     for i in range(0, B, step):
         v, S = _conv64(x[i:i + step], w, b, stride, pad)
         ref = _act64(v, act)
-        E = 1.5 * 11 * U * S + (8 + 2 * v.abs()) * U * ref.abs()
-        bound = E * (1 + uo) + uo * ref.abs() + tiny
+        bound = _bound(v, S, ref, x.dtype)
         if spread is not None:
             a, c = outs[0][0][i:i + step], outs[1][0][i:i + step]
             d = (a.double() - c.double()).abs()
@@ -253,7 +265,7 @@ def _check(x, w, b, act, stride, pad, outs, tag='', spread=None):
             spread['differ'] = spread.get('differ', 0) + int((d > 0).sum())
             spread['share'] = max(spread.get('share', 0.0), float((d / bound).max()))
             spread['ulp'] = max(spread.get('ulp', 0), int(((_ordered(a) - _ordered(c)).abs() * solid).max()))
-        del E, S, v
+        del S, v
         for y, mean in outs:
             assert y.shape[1:] == ref.shape[1:] and y.shape[0] == B and y.dtype == x.dtype
             yd = y[i:i + step].double()

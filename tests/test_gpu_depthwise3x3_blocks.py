@@ -134,13 +134,22 @@ def _conv_case(B, C, H, W, dtype, seed):
     return (x, w, b) + _conv64(x, w, b)
 
 
-def _case(B, C, H, W, dtype, act, seed):
-    x, w, b, v, S = _conv_case(B, C, H, W, dtype, seed)
+def _bound(v, S, dtype, act):
+    """(fp64 result, the bound of the module docstring) from _conv64's (v, S)."""
     ref = _act64(v, act)
     uo = U_OUT[dtype]
     E = 1.5 * 11 * U * S + (8 + 2 * v.abs()) * U * ref.abs()
-    bound = E * (1 + uo) + uo * ref.abs() + TINY[dtype]
-    return x, w, b, ref, bound
+    return ref, E * (1 + uo) + uo * ref.abs() + TINY[dtype]
+
+
+def _ref_and_bound(x, w, b, act):
+    """(fp64 result, bound) of any tensors: what _check is given (tests/conv_fuzz.py)."""
+    return _bound(*_conv64(x, w, b), x.dtype, act)
+
+
+def _case(B, C, H, W, dtype, act, seed):
+    x, w, b, v, S = _conv_case(B, C, H, W, dtype, seed)
+    return (x, w, b) + _bound(v, S, dtype, act)
 
 
 def _check(ref, bound, y, mean, tag):

@@ -71,12 +71,18 @@ def _reference(x, w, b, act, stride, pad):
     return _act64(v, act), v, S
 
 
-def _check(x, w, b, act, stride, pad, y, mean=None, tag=''):
+def _ref_and_bound(x, w, b, act, stride, pad):
+    """(fp64 result, the bound of the module docstring): what _check compares y with (tests/conv_fuzz.py)."""
     ref, v, S = _reference(x, w, b, act, stride, pad)
-    assert y.shape == ref.shape and y.dtype == x.dtype
     u, uo = 2.0 ** -24, U_OUT[x.dtype]
     E = 1.5 * 27 * u * S + (8 + 2 * v.abs()) * u * ref.abs()
-    bound = E * (1 + uo) + uo * ref.abs() + 2.0 ** -25
+    return ref, E * (1 + uo) + uo * ref.abs() + 2.0 ** -25
+
+
+def _check(x, w, b, act, stride, pad, y, mean=None, tag=''):
+    ref, bound = _ref_and_bound(x, w, b, act, stride, pad)
+    assert y.shape == ref.shape and y.dtype == x.dtype
+    u = 2.0 ** -24
     err = (y.double() - ref).abs()
     share = float((err / bound).max())
     print(f'[k15] {tag} {tuple(x.shape)} {str(x.dtype)[6:]} act={act} s={stride} pad={pad}: '

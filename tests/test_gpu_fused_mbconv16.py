@@ -78,8 +78,8 @@ def _ulp(v, dt):
     return torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(torch.finfo(dt).tiny))) - _MANT[dt])
 
 
-def _check_fp64(x, w3, b3, act, stride, w1, b1, r, got, label):
-    """The module docstring's bound, every element."""
+def _reference(x, w3, b3, act, stride, w1, b1, r):
+    """(fp64 result, the module docstring's bound)."""
     dt = x.dtype
     K3, Cmid = 9 * x.shape[1], w1.shape[1]
     z3 = F.conv2d(x.double(), w3.double(), None, stride, 1) + b3.double()[None, :, None, None]
@@ -94,8 +94,14 @@ def _check_fp64(x, w3, b3, act, stride, w1, b1, r, got, label):
     if r is not None:
         ref = ref + r.double()
         rabs = r.double().abs()
-    bound = carried + 1.1 * Cmid * 2.0 ** -24 * s1 + 2.0 ** -23 * (s1 + rabs) + 1e-6 * ref.abs() + 2.0 ** -24 \
+    return ref, carried + 1.1 * Cmid * 2.0 ** -24 * s1 + 2.0 ** -23 * (s1 + rabs) + 1e-6 * ref.abs() + 2.0 ** -24 \
         + _ulp(ref, dt)
+
+
+def _check_fp64(x, w3, b3, act, stride, w1, b1, r, got, label):
+    """The module docstring's bound, every element (tests/conv_fuzz.py uses the same two functions)."""
+    dt = x.dtype
+    ref, bound = _reference(x, w3, b3, act, stride, w1, b1, r)
     assert got.shape == ref.shape and got.dtype == dt
     err = (got.double() - ref).abs()
     print(f'k16h fp64 {label} {dt}: max err / bound = {float((err / bound).max()):.3f}')

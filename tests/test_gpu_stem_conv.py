@@ -104,12 +104,17 @@ def _reference(p, w, b):
     return z, s
 
 
-def _check(z, s, act, got, dt, what, worst):
+def _bound(z, s, act, dt):
+    """(fp64 result, the bound of the module docstring) from _reference's (z, s)."""
     K = 28 if dt == F32 else 32
     ref = _TORCH_ACT[act](z)
     tiny = torch.finfo(dt).tiny
     ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp_min(tiny))) - _MANT[dt])
-    bound = ulp + _LIP[act] * (K + 1) * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24 * z.abs() + 2.0 ** -23
+    return ref, ulp + _LIP[act] * (K + 1) * 2.0 ** -24 * s + 1e-6 * ref.abs() + 2.0 ** -24 * z.abs() + 2.0 ** -23
+
+
+def _check(z, s, act, got, dt, what, worst):
+    ref, bound = _bound(z, s, act, dt)
     assert got.shape == ref.shape and got.dtype == dt and got.is_contiguous()
     err = (got.double() - ref).abs()
     share = float((err / bound).max())
