@@ -760,6 +760,39 @@ int mtr_conv3x3s2_bias_act(const void* x, const float* w_packed /*[Cin/4][Cout][
  * weight), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_conv3x3s2_lds_bytes(long long B, int Cin, int Cout, int H, int W);
 
+/* K25h (outside the reference's hot path, like K10): the 1x1 expand convolution of an MBConv block and the depthwise
+ * 3x3 stride-1 padding-1 convolution behind it, of f16 / bf16 tensors, as ONE launch; the Cmid-wide activation between
+ * them stays in LDS (no workspace, nothing allocated, graph-capturable):
+ *   mid[b, c, p] = rnd16(act1(bias1[c] + sum_k w1[c, k] * x[b, k, p]))                                     c < Cmid
+ *   y[b, c, p]   = rnd16(act2(bias_dw[c] + sum_{ky, kx} w_dw[c, ky, kx] * mid[b, c, p + (ky - 1, kx - 1)]))
+ *   row_mean[b, c] = (1 / (H W)) * sum_p f32(y[b, c, p])                                      (where row_mean != NULL)
+ * y and row_mean have the BITS of mtr_conv1x1_bias_act16(x, w1, bias1, NULL, NULL, act1) followed by
+ * mtr_depthwise3x3_bias_act(mid, w_dw, bias_dw, act2, stride 1, pad 1, row_mean): the same 16-k MFMA steps in the same
+ * order, the intermediate rounded to 16 bits once, the depthwise accumulator started at the bias and nine fmaf in
+ * (ky, kx) order, the mean from the rounded outputs in the order of K11's stride-1 block kernel.
+ * x [B, Cin, H, W] and y [B, Cmid, H, W] (NCHW, contiguous, 16-byte aligned) in `dtype` (MTR_F16 or MTR_BF16, else
+ * MTR_E_DTYPE); w1 [Cmid][Cin] in `dtype`, 16-byte aligned; bias1 [Cmid], w_dw [Cmid][3][3], bias_dw [Cmid] and
+ * row_mean [B][Cmid] f32.  act1_code / act2_code as the `act` of mtr_bias_act_nchw, else MTR_E_PARAM.
+ * MTR_E_SHAPE (the caller keeps the two-kernel chain) unless: Cin % 8 == 0; H / 4 and W / 4 powers of two with
+ * H W <= 256 (the planes K11 runs on its block kernel, up to 16x16: 4x4, 8x8, 16x16, 8x16, 16x4, ...); B Cmid < 2^24.
+ * A NULL x, w1, bias1, w_dw, bias_dw or y is MTR_E_NULL; y overlapping x is MTR_E_PARAM.  Checked in the order NULL,
+ * dtype, shape, parameters, alignment, overlap, on the host before anything is enqueued; B == 0 returns MTR_OK without
+ * a launch.  No atomics, no split-K; only enqueues on `stream`: the same inputs give the same bits for any batch index,
+ * on every call and graph replay. */
+int mtr_expand_dw16(const void* x, int dtype, const void* w1 /*[Cmid][Cin]*/, const float* bias1, int act1_code,
+                    const float* w_dw /*[Cmid][3][3]*/, const float* bias_dw, int act2_code, long long B, int Cin,
+                    int Cmid, int H, int W, void* y, float* row_mean /* may be NULL */, mtr_stream_t stream);
+
+/* The same with the workgroup-to-image mapping chosen: -1 the library's own choice, 0 blockIdx = image * chunks +
+ * chunk, 1 the chunks of one image on one XCD (else MTR_E_PARAM).  The bits do not depend on it. */
+int mtr_expand_dw16_opts(const void* x, int dtype, const void* w1, const float* bias1, int act1_code,
+                         const float* w_dw, const float* bias_dw, int act2_code, long long B, int Cin, int Cmid, int H,
+                         int W, void* y, float* row_mean, mtr_stream_t stream, int mapping);
+
+/* The bytes of LDS one workgroup of mtr_expand_dw16 uses for this shape (the slice of the expanded activation), or 0
+ * where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_expand_dw16_lds_bytes(long long B, int Cin, int Cmid, int H, int W);
+
 /* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
  * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
  *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32

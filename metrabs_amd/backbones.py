@@ -465,8 +465,8 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate' or 'library': what the
-        # last forward ran (tests, A/B runs)
+        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate', 'k25h' (handed over to
+        # the depthwise layer behind) or 'library': what the last forward ran (tests, A/B runs)
         self.last_path = None
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
@@ -576,11 +576,27 @@ class ConvBiasAct(nn.Module):
             return None
         return 'k20' if self._k20_for_k13(x) else 'k13'
 
+    # set by fold_batchnorm(fuse_expand_depthwise=True) on the 1x1 expand of an MBConv block: the stride-1 3x3
+    # DepthwiseBiasAct directly behind this layer, which runs both layers as one launch (K25h) -- a reference, as
+    # Preproc.hand_to: nothing is registered twice
+    hand_to = ()
+
+    def hands_over(self, x, residual=None, pre=None, defer_epilogue=False):
+        """Whether forward(x, ...) leaves `x` untouched to the depthwise layer behind (K25h): an armed expand, called
+        as the expand of a block is called, and that layer says dw.k25h_takes(x, self)."""
+        return (residual is None and pre is None and not defer_epilogue
+                and any(dw.k25h_takes(x, self) for dw in self.hand_to))
+
     def path(self, x, residual=None, pre=None, defer_epilogue=False):
-        """Which path forward(x, residual, pre=pre, defer_epilogue=defer_epilogue) runs, as last_path will say it: the
-        kernel_for(x) if its epilogue can add `residual` ('_gate' behind it where the squeeze-excite block in front
-        handed the gate of this very `x` over), 'library' otherwise.  `x` as it enters the convolution: the first
-        convolution of a 16-bit copy casts before it asks."""
+        """Which path forward(x, residual, pre=pre, defer_epilogue=defer_epilogue) runs, as last_path will say it:
+        'k25h' where an armed expand hands `x` over, else the kernel_for(x) if its epilogue can add `residual` ('_gate'
+        behind it where the squeeze-excite block in front handed the gate of this very `x` over), 'library' otherwise.
+        `x` as it enters the convolution: the first convolution of a 16-bit copy casts before it asks."""
+        if self.hands_over(x, residual, pre, defer_epilogue):
+            return 'k25h'
+        return ConvBiasAct._own_path(self, x, residual, pre, defer_epilogue)
+
+    def _own_path(self, x, residual=None, pre=None, defer_epilogue=False):
         kernel = None if defer_epilogue or not _addable(residual, x) else self.kernel_for(x)
         if kernel is None:
             return 'library'
@@ -613,7 +629,17 @@ class ConvBiasAct(nn.Module):
         """defer_epilogue / pre: between the two layers of an armed FusedMBConv (FusedMBConv._forward_pre) only.
         defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way:
         its "+ bias, activation" is applied here, inside K13 or K20 where one takes `x`, by K10 in front of the library
-        path otherwise."""
+        path otherwise.  An armed expand (hand_to) whose depthwise layer takes `x` hands it over and returns it untouched:
+        that layer's forward runs both (K25h)."""
+        if self.hands_over(x, residual, pre, defer_epilogue):
+            # decided here, once: the depthwise layer runs this convolution, its bias and its activation itself
+            self.hand_to[0].hand_over(x, self)
+            self.last_path = 'k25h'
+            return x
+        return self.forward_here(x, residual, defer_epilogue, pre)
+
+    def forward_here(self, x, residual=None, defer_epilogue=False, pre=None):
+        """forward without the hand-over: this layer's own convolution, whatever stands behind it."""
         if defer_epilogue:
             self.last_path = 'library'
             return self.conv(x)
@@ -622,7 +648,7 @@ class ConvBiasAct(nn.Module):
             if x is not x0 and self._gate is not None and self._gate[0] is x0:
                 self._gate = (x, self._gate[1])  # (a gate handed over for the tensor stays with its cast copy)
         # (ConvBiasAct's own order: a subclass has asked for the kernel it puts in front, and of the tensor as it came)
-        path = self.last_path = ConvBiasAct.path(self, x, residual, pre)
+        path = self.last_path = ConvBiasAct._own_path(self, x, residual, pre)
         held, self._gate = self._gate, None
         gate = held[1] if pre is None and held is not None and held[0] is x else None
         if path == 'library':
@@ -915,7 +941,7 @@ class DepthwiseBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False
         self._mean = None
-        self.last_path = None  # 'k11', 'k15', 'k18' or 'library': what the last forward ran (tests, A/B runs)
+        self.last_path = None  # 'k11', 'k15', 'k18', 'k25h' or 'library': what the last forward ran (tests, A/B runs)
         # fold_batchnorm(block_depthwise=True) sets this on the k = 3, stride-1, padding-1 layers: they run K18 on
         # the planes it takes and K11's block kernel refuses -- the bits of K11's generic kernel, which those planes
         # run on otherwise
@@ -941,9 +967,43 @@ class DepthwiseBiasAct(nn.Module):
                 and not kernels.k11_takes_block_kernel(H, W) and 0 < B * C < 2 ** 24
                 and (C, H, W) not in DepthwiseBiasAct.k18_slower)
 
+    # K25h (fold_batchnorm(fuse_expand_depthwise=True)): the class-wide switch, and the (Cin, Cmid, H, W) of the
+    # expand's input where K25h was not ahead of the chain K13h + K11 in every round of tools/expand_dw_ab.py: these
+    # keep the chain (EfficientNetV2-S batch 64 and MobileNetV3 batch 320 at 256 px, f16 and bf16, the same five in
+    # both; DESIGN.md section 30, profiles/r21a_expand_dw_ab.jsonl).  EfficientNetV2-L and other resolutions have not
+    # been timed
+    use_k25h = True
+    k25h_slower = frozenset({(128, 768, 16, 16), (160, 960, 16, 16), (80, 200, 16, 16), (80, 480, 16, 16),
+                             (112, 672, 16, 16)})
+    _handed = None
+
+    def k25h_takes(self, x, expand):
+        """Whether this layer runs `expand` (the armed 1x1 ConvBiasAct in front) and itself on `x`, the expand's input,
+        as one launch (K25h, expand_dw16.hip): a 3x3 stride-1 padding-1 layer without a folded ZeroPad2d, an inference
+        call on both weights, a CUDA NCHW-contiguous input of the copy's dtype that the expand would run on K13h with
+        no gate held, a plane K11 runs on its block kernel, a shape the C entry accepts and that is not listed as
+        slower.  Everything else runs the chain: today's branch, today's bits."""
+        c = expand.conv
+        if not (DepthwiseBiasAct.use_k25h and self.k == 3 and self.stride == 1 and self.pad == 1 and self.pads is None
+                and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
+                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+            return False
+        held = expand._gate
+        if (held is not None and held[0] is x) or expand.kernel_for(x) != 'k13h':
+            return False
+        B, K, H, W = x.shape
+        return (kernels.k11_takes_block_kernel(H, W)
+                and (K, c.out_channels, H, W) not in DepthwiseBiasAct.k25h_slower
+                and kernels.expand_depthwise16_supported(x, c.weight))
+
+    def hand_over(self, x, expand):
+        """From the armed expand in front: `x` comes WITHOUT that convolution applied; the next forward(x) runs it."""
+        self._handed = (x, expand)
+
     def path(self, x):
-        """Which path forward(x) runs, as last_path will say it: 'k18' (an armed 3x3 layer), then 'k11' (3x3) or 'k15'
-        (5x5), then 'library' (the torch ops)."""
+        """Which path forward(x) runs on an input that was not handed over, as last_path will say it: 'k18' (an armed
+        3x3 layer), then 'k11' (3x3) or 'k15' (5x5), then 'library' (the torch ops).  ('k25h': forward, on the input
+        an armed expand handed over.)"""
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
         ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
         if not (x.is_cuda and x.is_contiguous() and ow % 4 == 0 and x.dtype in _FLOATS):
@@ -956,6 +1016,19 @@ class DepthwiseBiasAct(nn.Module):
         return 'library'
 
     def forward(self, x):
+        held, self._handed = self._handed, None
+        if held is not None and held[0] is x:  # the expand in front left its convolution to this module
+            expand = held[1]
+            if self.k25h_takes(x, expand):
+                self.last_path = 'k25h'
+                out = kernels.expand_depthwise16(x, expand.conv.weight, expand.bias, expand.act_name, self.weight,
+                                                 self.bias, self.act_name, want_mean=self.emit_mean)
+                if not self.emit_mean:
+                    return out
+                self._mean = out
+                return out[0]
+            # (the expand asked k25h_takes(x) before it handed x over; whatever changed since: never un-expanded)
+            x = expand.forward_here(x)
         path = self.last_path = self.path(x)
         if path != 'library':
             if path == 'k18':
@@ -1166,6 +1239,22 @@ def _arm_deep_projects(folded):
             m.deep_projects = True
 
 
+def _arm_expand_depthwise(folded):
+    """fuse_expand_depthwise: every plain 1x1 ConvBiasAct that emits no mean and stands directly in front of a 3x3,
+    stride-1, padding-1 DepthwiseBiasAct of as many channels without a folded ZeroPad2d -- the expand and depthwise
+    layers of the stride-1 MBConv blocks: 28 pairs of EfficientNetV2-S, 59 of -L, 6 of MobileNetV3, none of ResNet-18
+    -- is armed to hand its input to that layer, which runs both as ONE launch (K25h, both .last_path 'k25h') where
+    DepthwiseBiasAct.k25h_takes says so: the bits of the chain K13h + K11, the expanded activation kept in LDS.  The
+    chain runs everywhere else (24x24, 12x12 and 64x64 planes, the expand shapes of ConvBiasAct.k13h_slower, CPU, ...).
+    The stride-2 blocks have their folded ZeroPad2d (an Identity) between the two layers and stay unarmed."""
+    for _, _, a, b in _adjacent_children(folded):
+        expand, dw = _only_layer(a), _only_layer(b)
+        if type(expand) is ConvBiasAct and not expand.emit_mean and _plain_1x1(expand.conv) \
+                and isinstance(dw, DepthwiseBiasAct) and dw.k == 3 and dw.stride == 1 and dw.pad == 1 \
+                and dw.pads is None and dw.weight.shape[0] == expand.conv.out_channels:
+            expand.hand_to = (dw,)
+
+
 def _arm_split_gemm(folded):
     """split_gemm: every plain 1x1 ConvBiasAct that emits no mean -- the expand, project and head-side 1x1 layers --
     runs K20 (.last_path 'k20' / 'k20_gate'; an armed FusedMBConv block reports 'k20_pre') wherever K13 would take the
@@ -1196,12 +1285,12 @@ _NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
           'f32': (lambda fused, dtype: fused and dtype is None, 'fused_epilogue=True and an f32 copy (no dtype=)')}
 _OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
                  ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'),
-                 ('strided3x3', 'f32'))
+                 ('strided3x3', 'f32'), ('fuse_expand_depthwise', '16bit'))
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                    block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
-                   strided3x3=False):
+                   strided3x3=False, fuse_expand_depthwise=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -1226,8 +1315,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     split_gemm=True (needs fused_epilogue=True and an f32 copy): the f32 1x1 layers on K20 (_arm_split_gemm).
     strided3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-2 layers with Cin % 4 == 0 as an
     implicit GEMM on the f32 MFMA, K22 (_replace_strided3x3).
+    fuse_expand_depthwise=True (needs a 16-bit dtype): the 1x1 expand and the stride-1 depthwise 3x3 layer of an MBConv
+    block as one launch, K25h (_arm_expand_depthwise).
     The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3; 16-bit:
-    fuse_blocks, fuse_stem, block_depthwise, deep_projects): no two of them arm the same field of the same module, and
+    fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise): no two of them arm the same field of the same module, and
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
     module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
@@ -1244,7 +1335,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         raise ValueError('fold_batchnorm: a 16-bit copy (dtype=) needs fused_epilogue=True')
     options = dict(fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
                    deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
-                   strided3x3=strided3x3)
+                   strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise)
     for option, need in _OPTION_NEEDS:
         met, text = _NEEDS[need]
         if options[option] and not met(fused_epilogue, dtype):
@@ -1270,6 +1361,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         _arm_deep_projects(folded)
     if split_gemm:
         _arm_split_gemm(folded)
+    if fuse_expand_depthwise:
+        _arm_expand_depthwise(folded)
     if fuse_stem:
         _fuse_stem(folded)
     return folded

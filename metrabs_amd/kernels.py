@@ -985,6 +985,64 @@ def fused_mbconv16(x, w3_packed, bias3, act, stride, w1, bias1, residual=None, o
     return out
 
 
+# K25h: the 1x1 expand of an MBConv block of f16 / bf16 tensors (K13h) and the depthwise 3x3 stride-1 layer behind it
+# (K11's block kernel) as one launch (csrc/expand_dw16.hip)
+
+EXPAND_DW16_MAPPINGS = {'auto': -1, 'plain': 0, 'xcd': 1}
+
+
+def expand_depthwise16_supported(x, w1):
+    """Whether mtr_expand_dw16 takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous, both
+    16-byte aligned, Cin a multiple of 8, an [.., H, W] plane K11 runs on its stride-1 block kernel
+    (k11_takes_block_kernel) of at most 256 positions, fewer than 2^24 planes of output (its MTR_E_DTYPE /
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w1` is the expand's weight, [Cmid, Cin] or
+    [Cmid, Cin, 1, 1]."""
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
+            or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if w1.numel() != w1.shape[0] * K:
+        return False
+    return _lib.load().mtr_expand_dw16_lds_bytes(B, K, w1.shape[0], H, W) > 0
+
+
+def expand_depthwise16(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False, out=None, mapping='auto'):
+    """y = act2(depthwise_conv3x3(act1(conv1x1(x, w1) + bias1), w_dw, stride 1, padding 1) + bias_dw) in one launch
+    on the current stream (+ the [B, Cmid] f32 mean of y over H*W if want_mean), for f16 / bf16: x [B, Cin, H, W]
+    NCHW-contiguous, w1 [Cmid, Cin] (or the [Cmid, Cin, 1, 1] conv weight) in x's dtype, bias1 [Cmid] f32, w_dw
+    [Cmid, 1, 3, 3] or [Cmid, 3, 3] and bias_dw [Cmid] (taken as f32, as depthwise3x3_bias_act takes them).  The
+    expanded activation stays on the chip, rounded to x's dtype once; y and the mean have the bits of
+    conv1x1_bias_act16 followed by depthwise3x3_bias_act(.., 1, 1, want_mean=True) (the same on every call and graph
+    replay, and for every `mapping`: a key of EXPAND_DW16_MAPPINGS).  What the kernel does not take raises
+    (expand_depthwise16_supported asks first); there is no fallback in here."""
+    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
+    code = EXPAND_DW16_MAPPINGS[mapping]
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('expand_depthwise16: x must be [B, Cin, H, W], NCHW-contiguous')
+    B, K, H, W = x.shape
+    Cmid = w1.shape[0]
+    w1 = w1.reshape(Cmid, -1)
+    if w1.shape[1] != K:
+        raise ValueError(f'expand_depthwise16: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
+    if w1.dtype != x.dtype:
+        raise ValueError(f'expand_depthwise16: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
+    if w_dw.numel() != Cmid * 9:
+        raise ValueError(f'expand_depthwise16: the depthwise weight must be [{Cmid}, 3, 3], got {tuple(w_dw.shape)}')
+    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
+        raise ValueError(f'expand_depthwise16: biases have {bias1.numel()} and {bias_dw.numel()} elements, expected '
+                         f'{Cmid} each')
+    out = _residual_and_out('expand_depthwise16', x, (B, Cmid, H, W), None, out)
+    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
+    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
+            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
+            _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
+    if code < 0:
+        check(_lib.load().mtr_expand_dw16(*args), 'mtr_expand_dw16')
+    else:
+        check(_lib.load().mtr_expand_dw16_opts(*args, code), 'mtr_expand_dw16_opts')
+    return (out, mean) if want_mean else out
+
+
 # K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one
 # launch (csrc/stem_conv.hip)
 

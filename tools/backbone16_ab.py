@@ -57,14 +57,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22'],
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22', 'k25h'],
                     default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
                          "k18: without vs with block_depthwise; deepk: without vs with deep_projects; "
                          "k19 (--dtype f32): the f32 copy folded without vs with winograd3x3; "
                          "k20 (--dtype f32): the f32 copy folded without vs with split_gemm; "
-                         "k22 (--dtype f32): the f32 copy folded without vs with strided3x3")
+                         "k22 (--dtype f32): the f32 copy folded without vs with strided3x3; "
+                         "k25h: the 16-bit copy folded without vs with fuse_expand_depthwise")
     ap.add_argument('--winograd3x3', action='store_true',
                     help='--ab k20, --ab k22: fold both arms with winograd3x3=True too')
     ap.add_argument('--out', required=True)
@@ -149,6 +150,12 @@ def main():
         est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
                                                    deep_projects=True)
         assert any(isinstance(m, ConvBiasAct) and m.deep_projects for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k25h':                                        # both arms the 16-bit copy, B with its MBConv pairs armed
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   fuse_expand_depthwise=True)
+        assert any(isinstance(m, ConvBiasAct) and m.hand_to for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -219,6 +226,12 @@ def main():
         paths = [m.last_path for m in est_b.crop_model.backbone.modules()
                  if isinstance(m, FusedMBConv) and m.fused_pair]
         row = dict(kind='paths', ab='k16h', k16h=paths.count('k16h'), chain=paths.count('chain'))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k25h':
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules() if isinstance(m, ConvBiasAct) and m.hand_to]
+        row = dict(kind='paths', ab='k25h', equal_poses=bool(torch.equal(p_a, p_b)),
+                   b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
         print(json.dumps(row), flush=True)
         rows.append(row)
     if args.ab == 'k17':
