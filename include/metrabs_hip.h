@@ -793,6 +793,34 @@ int mtr_expand_dw16_opts(const void* x, int dtype, const void* w1, const float* 
  * where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_expand_dw16_lds_bytes(long long B, int Cin, int Cmid, int H, int W);
 
+/* K26h (outside the reference's hot path, like K10): mtr_expand_dw16's function -- the same three formulas, arguments,
+ * checks and error codes -- on the planes it refuses because K11 runs them on its GENERIC kernel (24x24 and 12x12 of
+ * the EfficientNetV2 family at 384 px).  y and row_mean have the BITS of mtr_conv1x1_bias_act16(x, w1, bias1, NULL,
+ * NULL, act1) followed by mtr_depthwise3x3_bias_act(mid, w_dw, bias_dw, act2, stride 1, pad 1, row_mean) on such a
+ * plane: the depthwise accumulator started at 0, nine fmaf with ky outer and kx inner, the bias added last, the mean in
+ * the generic kernel's order (groups of four outputs left to right, lane s of lpp adding groups s, s + 64, ..., the xor
+ * butterfly).  They are therefore also the bits of mtr_conv1x1_bias_act16 + mtr_depthwise3x3_blocks_bias_act.
+ * MTR_E_SHAPE (the caller keeps the two-kernel chain) unless: Cin % 8 == 0; W % 4 == 0; H W % 8 == 0; H <= 32, W <= 32,
+ * H W <= 576; the plane is NOT one K11 runs on its block kernel (H / 4 and W / 4 powers of two with at most 16 blocks
+ * per row and 64 per plane: mtr_expand_dw16's planes, 32x16, 16x32, ...); B Cmid < 2^30.  A NULL x, w1, bias1, w_dw,
+ * bias_dw or y is MTR_E_NULL; act1_code / act2_code outside 0..3 are MTR_E_PARAM; y overlapping x is MTR_E_PARAM.
+ * Checked in the order NULL, dtype, shape, parameters, alignment, overlap, on the host before anything is enqueued;
+ * B == 0 returns MTR_OK without a launch.  No atomics, no split-K, no workspace; only enqueues on `stream`: the same
+ * inputs give the same bits for any batch index, on every call and graph replay. */
+int mtr_expand_dw16_planes(const void* x, int dtype, const void* w1 /*[Cmid][Cin]*/, const float* bias1, int act1_code,
+                           const float* w_dw /*[Cmid][3][3]*/, const float* bias_dw, int act2_code, long long B,
+                           int Cin, int Cmid, int H, int W, void* y, float* row_mean /* may be NULL */,
+                           mtr_stream_t stream);
+
+/* The same with the workgroup-to-image mapping chosen, as in mtr_expand_dw16_opts.  The bits do not depend on it. */
+int mtr_expand_dw16_planes_opts(const void* x, int dtype, const void* w1, const float* bias1, int act1_code,
+                                const float* w_dw, const float* bias_dw, int act2_code, long long B, int Cin, int Cmid,
+                                int H, int W, void* y, float* row_mean, mtr_stream_t stream, int mapping);
+
+/* The bytes of LDS one workgroup of mtr_expand_dw16_planes uses for this shape, or 0 where the entry answers
+ * MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_expand_dw16_planes_lds_bytes(long long B, int Cin, int Cmid, int H, int W);
+
 /* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
  * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
  *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32

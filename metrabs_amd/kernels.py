@@ -1043,6 +1043,60 @@ def expand_depthwise16(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False,
     return (out, mean) if want_mean else out
 
 
+# K26h: the same pair on the planes K11 runs on its generic kernel, 24x24 and 12x12 among them
+# (csrc/expand_dw16_planes.hip)
+
+def expand_depthwise16_planes_supported(x, w1):
+    """Whether mtr_expand_dw16_planes takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous,
+    both 16-byte aligned, Cin a multiple of 8, an [.., H, W] plane with W % 4 == 0, H W % 8 == 0, H and W at most 32
+    and H W at most 576 that K11 does NOT run on its stride-1 block kernel (k11_takes_block_kernel), fewer than 2^30
+    planes of output (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w1` is the
+    expand's weight, [Cmid, Cin] or [Cmid, Cin, 1, 1]."""
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
+            or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if w1.numel() != w1.shape[0] * K:
+        return False
+    return _lib.load().mtr_expand_dw16_planes_lds_bytes(B, K, w1.shape[0], H, W) > 0
+
+
+def expand_depthwise16_planes(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False, out=None, mapping='auto'):
+    """expand_depthwise16 for the planes it refuses (K26h): the same arguments and result, in one launch on the
+    current stream.  y and the mean have the bits of conv1x1_bias_act16 followed by depthwise3x3_bias_act(.., 1, 1,
+    want_mean=True) on such a plane -- K11's generic kernel, so also the bits of depthwise3x3_blocks_bias_act behind
+    conv1x1_bias_act16 -- the same on every call and graph replay, and for every `mapping` (a key of
+    EXPAND_DW16_MAPPINGS).  What the kernel does not take raises (expand_depthwise16_planes_supported asks first);
+    there is no fallback in here."""
+    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
+    code = EXPAND_DW16_MAPPINGS[mapping]
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('expand_depthwise16_planes: x must be [B, Cin, H, W], NCHW-contiguous')
+    B, K, H, W = x.shape
+    Cmid = w1.shape[0]
+    w1 = w1.reshape(Cmid, -1)
+    if w1.shape[1] != K:
+        raise ValueError(f'expand_depthwise16_planes: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
+    if w1.dtype != x.dtype:
+        raise ValueError(f'expand_depthwise16_planes: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
+    if w_dw.numel() != Cmid * 9:
+        raise ValueError(f'expand_depthwise16_planes: the depthwise weight must be [{Cmid}, 3, 3], got '
+                         f'{tuple(w_dw.shape)}')
+    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
+        raise ValueError(f'expand_depthwise16_planes: biases have {bias1.numel()} and {bias_dw.numel()} elements, '
+                         f'expected {Cmid} each')
+    out = _residual_and_out('expand_depthwise16_planes', x, (B, Cmid, H, W), None, out)
+    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
+    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
+            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
+            _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
+    if code < 0:
+        check(_lib.load().mtr_expand_dw16_planes(*args), 'mtr_expand_dw16_planes')
+    else:
+        check(_lib.load().mtr_expand_dw16_planes_opts(*args, code), 'mtr_expand_dw16_planes_opts')
+    return (out, mean) if want_mean else out
+
+
 # K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one
 # launch (csrc/stem_conv.hip)
 

@@ -57,7 +57,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22', 'k25h'],
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22', 'k25h',
+                                     'k26h'],
                     default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
@@ -65,7 +66,11 @@ def main():
                          "k19 (--dtype f32): the f32 copy folded without vs with winograd3x3; "
                          "k20 (--dtype f32): the f32 copy folded without vs with split_gemm; "
                          "k22 (--dtype f32): the f32 copy folded without vs with strided3x3; "
-                         "k25h: the 16-bit copy folded without vs with fuse_expand_depthwise")
+                         "k25h: the 16-bit copy folded without vs with fuse_expand_depthwise; "
+                         "k26h: the 16-bit copy folded without vs with fuse_expand_depthwise_planes (--config 4, or "
+                         "--config 1 --res 384)")
+    ap.add_argument('--res', type=int, default=None, help='crop side handed to bench.py (its --res) instead of the '
+                                                          "config's own")
     ap.add_argument('--winograd3x3', action='store_true',
                     help='--ab k20, --ab k22: fold both arms with winograd3x3=True too')
     ap.add_argument('--out', required=True)
@@ -82,7 +87,8 @@ def main():
     import bench
     from metrabs_amd.backbones import Conv3x3BiasAct, ConvBiasAct, DepthwiseBiasAct, fold_batchnorm
     dt = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': None}[args.dtype]
-    argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype]
+    argv, sys.argv = sys.argv, ['bench.py', '--config', str(args.config), '--precision', args.dtype] \
+        + ([] if args.res is None else ['--res', str(args.res)])
     bargs = bench.parse_args()
     sys.argv = argv
     dev = torch.device('cuda')
@@ -156,6 +162,12 @@ def main():
         est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
                                                    fuse_expand_depthwise=True)
         assert any(isinstance(m, ConvBiasAct) and m.hand_to for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k26h':                                        # the same, armed for the planes of a 384 px input
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   fuse_expand_depthwise_planes=True)
+        assert any(isinstance(m, ConvBiasAct) and m.hand_planes_to for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -231,6 +243,14 @@ def main():
     if args.ab == 'k25h':
         paths = [m.last_path for m in est_b.crop_model.backbone.modules() if isinstance(m, ConvBiasAct) and m.hand_to]
         row = dict(kind='paths', ab='k25h', equal_poses=bool(torch.equal(p_a, p_b)),
+                   b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k26h':
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules()
+                 if isinstance(m, ConvBiasAct) and m.hand_planes_to]
+        row = dict(kind='paths', ab='k26h', res=bargs.res, backbone=bargs.backbone, batch=bargs.batch,
+                   equal_poses=bool(torch.equal(p_a, p_b)),
                    b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
         print(json.dumps(row), flush=True)
         rows.append(row)

@@ -14,6 +14,14 @@ measured 6.29 TB/s copy rate of an MI355X).  `slower` is the rule of DepthwiseBi
 the chain in every round; a key is listed when that holds in f16 or in bf16 (the last line printed collects them).
 K25h's two workgroup-to-image mappings ('plain', 'xcd') are timed the same way as a third and fourth arm
 (kernels.expand_depthwise16(mapping=)); the library's own choice is whichever the entry resolves -1 to.
+
+    python tools/expand_dw_ab.py --kernel k26h --out OUT.jsonl
+
+does the same for fold_batchnorm(fuse_expand_depthwise_planes=True), K26h (kernels.expand_depthwise16_planes), on the
+384 px planes: EfficientNetV2-L at batch 32 and -S at batch 64.  The chain there is K13h + K11's generic kernel; one
+more arm, 'k18', is K13h + K18 (kernels.depthwise3x3_blocks_bias_act, what block_depthwise=True runs for the pair) and
+is recorded beside the others.  `slower` and the last line are the rule of DepthwiseBiasAct.k26h_slower, against the
+chain; chain_spread is the chain's largest round over its smallest, the noise floor.
 """
 import argparse
 import json
@@ -22,28 +30,37 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HBM_TBS = 6.29
-WORKLOADS = [('effnetv2-s', 64, 256), ('mobilenetv3', 320, 256)]
+# per kernel: the fold_batchnorm option, the expand's field, the class switch and list of DepthwiseBiasAct, its question,
+# the wrapper and the LDS query, and the (backbone, batch, px) measured
+KERNELS = {
+    'k25h': dict(option='fuse_expand_depthwise', field='hand_to', switch='use_k25h', slower='k25h_slower',
+                 takes='k25h_takes', fn='expand_depthwise16', lds='mtr_expand_dw16_lds_bytes',
+                 workloads=[('effnetv2-s', 64, 256), ('mobilenetv3', 320, 256)]),
+    'k26h': dict(option='fuse_expand_depthwise_planes', field='hand_planes_to', switch='use_k26h',
+                 slower='k26h_slower', takes='k26h_takes', fn='expand_depthwise16_planes',
+                 lds='mtr_expand_dw16_planes_lds_bytes', workloads=[('effnetv2-l', 32, 384), ('effnetv2-s', 64, 384)]),
+}
 
 
-def armed_pairs(net, res):
+def armed_pairs(net, res, cfg):
     """{(Cin, Cmid, H, W): [(expand, depthwise), ...]} of the armed pairs of `net` at `res` px."""
     import torch
     from metrabs_amd import backbones
     out = {}
     hooks = []
     for m in net.modules():
-        if isinstance(m, backbones.ConvBiasAct) and m.hand_to:
+        if isinstance(m, backbones.ConvBiasAct) and getattr(m, cfg['field']):
             def hook(mod, args):
                 x = args[0]
                 key = (mod.conv.in_channels, mod.conv.out_channels, x.shape[2], x.shape[3])
-                out.setdefault(key, []).append((mod, mod.hand_to[0]))
+                out.setdefault(key, []).append((mod, getattr(mod, cfg['field'])[0]))
             hooks.append(m.register_forward_pre_hook(hook))
-    backbones.DepthwiseBiasAct.use_k25h = False
+    setattr(backbones.DepthwiseBiasAct, cfg['switch'], False)
     try:
         with torch.inference_mode():
             net(torch.rand(1, 3, res, res, device='cuda'))
     finally:
-        backbones.DepthwiseBiasAct.use_k25h = True
+        setattr(backbones.DepthwiseBiasAct, cfg['switch'], True)
     for h in hooks:
         h.remove()
     return out
@@ -54,13 +71,16 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--dtypes', default='f16,bf16')
+    ap.add_argument('--kernel', choices=sorted(KERNELS), default='k25h')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
+    kn, cfg = args.kernel, KERNELS[args.kernel]
     sys.path.insert(0, ROOT)
     import torch
     from metrabs_amd import backbones, kernels
     DW = backbones.DepthwiseBiasAct
-    listed, DW.k25h_slower = DW.k25h_slower, frozenset()   # measure every shape, listed or not
+    listed = getattr(DW, cfg['slower'])
+    setattr(DW, cfg['slower'], frozenset())   # measure every shape, listed or not
     rows, losers = [], set()
 
     def captured(fn):
@@ -87,13 +107,13 @@ def main():
         return ev[0].elapsed_time(ev[1]) * 1e3 / args.iters
 
     med = lambda v: sorted(v)[len(v) // 2]
-    for backbone, B, res in WORKLOADS:
+    for backbone, B, res in cfg['workloads']:
         for dname in args.dtypes.split(','):
             dt = {'f16': torch.float16, 'bf16': torch.bfloat16}[dname]
             net = backbones.fold_batchnorm(backbones.build_backbone(backbone).eval(), fused_epilogue=True, dtype=dt,
-                                           fuse_expand_depthwise=True).cuda()
+                                           **{cfg['option']: True}).cuda()
             g = torch.Generator(device='cuda').manual_seed(0)
-            for key, pairs in armed_pairs(net, res).items():
+            for key, pairs in armed_pairs(net, res, cfg).items():
                 Cin, Cmid, H, W = key
                 e, d = pairs[0]
                 x = torch.randn(B, Cin, H, W, device='cuda', generator=g).to(dt)
@@ -105,21 +125,27 @@ def main():
                     return d(e(x))
 
                 def mapped(mapping):
-                    return lambda: kernels.expand_depthwise16(x, e.conv.weight, e.bias, e.act_name, d.weight, d.bias,
-                                                              d.act_name, want_mean=d.emit_mean, mapping=mapping)
+                    return lambda: getattr(kernels, cfg['fn'])(x, e.conv.weight, e.bias, e.act_name, d.weight, d.bias,
+                                                               d.act_name, want_mean=d.emit_mean, mapping=mapping)
+
+                def k18():
+                    return kernels.depthwise3x3_blocks_bias_act(e.forward_here(x), d.weight, d.bias, d.act_name,
+                                                                want_mean=d.emit_mean)
 
                 with torch.inference_mode():
                     a = chain()
                     chain_paths = (e.last_path, d.last_path)
-                    supported = d.k25h_takes(x, e)
+                    supported = getattr(d, cfg['takes'])(x, e)
                     arms = {'chain': chain}
                     equal = None
+                    if kn == 'k26h':
+                        arms['k18'] = k18
                     if supported:
                         c = fused()
-                        assert (e.last_path, d.last_path) == ('k25h', 'k25h')
+                        assert (e.last_path, d.last_path) == (kn, kn)
                         torch.cuda.synchronize()
                         equal = bool(torch.equal(a, c))
-                        arms.update(k25h=fused, plain=mapped('plain'), xcd=mapped('xcd'))
+                        arms.update({kn: fused, 'plain': mapped('plain'), 'xcd': mapped('xcd')})
                     for _ in range(3):
                         for fn in arms.values():
                             fn()
@@ -128,7 +154,7 @@ def main():
                         for gr in graphs.values():
                             timed(gr)
                     t = {n: [] for n in graphs}
-                    for _ in range(args.rounds):   # alternated: chain, k25h, plain, xcd, chain, ...
+                    for _ in range(args.rounds):   # alternated: chain, (k18,) the kernel, plain, xcd, chain, ...
                         for n, gr in graphs.items():
                             t[n].append(timed(gr))
                     del graphs
@@ -139,30 +165,34 @@ def main():
                            act=e.act_name, mean=d.emit_mean, layers=len(pairs), chain_expand=chain_paths[0],
                            chain_depthwise=chain_paths[1], mbytes=round(byts / 1e6, 1), mid_mbytes=round(mid_mb, 1),
                            chain_us=round(med(t['chain']), 2), chain_us_rounds=[round(v, 2) for v in t['chain']],
-                           k25h_us=None, listed=key in listed)
+                           listed=key in listed, **{kn + '_us': None})
+                if 'k18' in t:
+                    row.update(chain_spread=round(max(t['chain']) / min(t['chain']), 4),
+                               k18_us=round(med(t['k18']), 2), k18_us_rounds=[round(v, 2) for v in t['k18']])
                 if supported:
-                    tk = med(t['k25h'])
-                    ahead_every_round = all(n < o for n, o in zip(t['k25h'], t['chain']))
-                    row.update(k25h_us=round(tk, 2), k25h_us_rounds=[round(v, 2) for v in t['k25h']],
+                    tk = med(t[kn])
+                    ahead_every_round = all(n < o for n, o in zip(t[kn], t['chain']))
+                    row.update({kn + '_us': round(tk, 2), kn + '_us_rounds': [round(v, 2) for v in t[kn]]})
+                    row.update(
                                plain_us_rounds=[round(v, 2) for v in t['plain']],
                                xcd_us_rounds=[round(v, 2) for v in t['xcd']],
                                speedup=round(med(t['chain']) / tk, 3), byte_floor_us=round(floor, 2),
                                share_of_byte_floor=round(floor / tk, 3), equal_bits=equal,
                                slower=not ahead_every_round,
-                               lds_bytes=int(kernels._lib.load().mtr_expand_dw16_lds_bytes(B, Cin, Cmid, H, W)))
+                               lds_bytes=int(getattr(kernels._lib.load(), cfg['lds'])(B, Cin, Cmid, H, W)))
                     if not ahead_every_round:
                         losers.add(key)
                 rows.append(row)
                 print(json.dumps(row), flush=True)
             del net
             torch.cuda.empty_cache()
-    DW.k25h_slower = listed
-    print(json.dumps(dict(k25h_slower=sorted(losers))), flush=True)
+    setattr(DW, cfg['slower'], listed)
+    print(json.dumps({cfg['slower']: sorted(losers)}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         for r in rows:
             f.write(json.dumps(r) + '\n')
-        f.write(json.dumps(dict(k25h_slower=sorted(losers))) + '\n')
+        f.write(json.dumps({cfg['slower']: sorted(losers)}) + '\n')
 
 
 if __name__ == '__main__':
