@@ -821,6 +821,30 @@ int mtr_expand_dw16_planes_opts(const void* x, int dtype, const void* w1, const 
  * MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_expand_dw16_planes_lds_bytes(long long B, int Cin, int Cmid, int H, int W);
 
+/* K27h (outside the reference's hot path, like K10): the 1x1 expand and the depthwise 3x3 layer behind it (stride 1 or
+ * 2, zero padding 1 on all four sides) as one launch on LARGE planes, WITHOUT a mean output: a workgroup owns a band of
+ * output rows of 32 expanded channels and recomputes the halo rows of the expand.
+ *   mid[b, c, p] = rnd16(act1(bias1[c] + sum_k w1[c, k] x[b, k, p]))
+ *   y[b, c, o]   = rnd16(act2(sum_{ky, kx} w_dw[c, ky, kx] mid[b, c, stride o + (ky - 1, kx - 1)] + bias_dw[c]))
+ * y [B, Cmid, H / stride, W / stride] has the BITS of mtr_conv1x1_bias_act16(x, w1, bias1, NULL, NULL, act1) followed
+ * by mtr_depthwise3x3_bias_act(mid, w_dw, bias_dw, act2, stride, pad 1, NULL) where that runs K11's generic kernel:
+ * the accumulator started at 0, nine fmaf with ky outer and kx inner, the bias added last, one rounding.
+ * MTR_E_SHAPE (the caller keeps the two-kernel chain) unless: stride 1 or 2; Cin % 8 == 0; H <= 128, W <= 128;
+ * B Cmid < 2^30; at stride 1 W % 4 == 0, W >= 4, H W % 8 == 0 and the plane is NOT one K11 runs on its block kernel
+ * (H / 4 and W / 4 powers of two with at most 16 blocks per row and 64 per plane); at stride 2 H even and W % 8 == 0.
+ * A NULL x, w1, bias1, w_dw, bias_dw or y is MTR_E_NULL; act1_code / act2_code outside 0..3 are MTR_E_PARAM; y
+ * overlapping x is MTR_E_PARAM.  Checked in the order NULL, dtype, shape, parameters, alignment (x, w1, y 16 bytes),
+ * overlap, on the host before anything is enqueued; B == 0 returns MTR_OK without a launch.  No atomics, no split-K, no
+ * workspace; only enqueues on `stream`: the same inputs give the same bits for any batch index, on every call and
+ * graph replay. */
+int mtr_expand_dw16_tiles(const void* x, int dtype, const void* w1 /*[Cmid][Cin]*/, const float* bias1, int act1_code,
+                          const float* w_dw /*[Cmid][3][3]*/, const float* bias_dw, int act2_code, long long B,
+                          int Cin, int Cmid, int H, int W, int stride, void* y, mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_expand_dw16_tiles uses for this shape, or 0 where the entry answers
+ * MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_expand_dw16_tiles_lds_bytes(long long B, int Cin, int Cmid, int H, int W, int stride);
+
 /* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
  * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
  *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32

@@ -465,7 +465,7 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate', 'k25h' / 'k26h' (handed over to
+        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate', 'k25h' / 'k26h' / 'k27h' (handed over to
         # the depthwise layer behind) or 'library': what the last forward ran (tests, A/B runs)
         self.last_path = None
 
@@ -583,27 +583,32 @@ class ConvBiasAct(nn.Module):
     # the same reference set by fold_batchnorm(fuse_expand_depthwise_planes=True): that layer runs both as one launch
     # on the planes K25h refuses (K26h).  A field of its own, so the two options never arm one field
     hand_planes_to = ()
+    # and by fold_batchnorm(fuse_expand_depthwise_tiles=True): that layer, of stride 1 or 2 and without a mean, runs
+    # both as one launch in bands of rows on the large planes the other two refuse (K27h).  Again a field of its own
+    hand_tiles_to = ()
 
     def _handed_kernel(self, x, residual=None, pre=None, defer_epilogue=False):
-        """'k25h' / 'k26h' where forward(x, ...) hands `x` over to the depthwise layer behind, else None.  The two
-        kernels' planes are disjoint."""
+        """'k25h' / 'k26h' / 'k27h' where forward(x, ...) hands `x` over to the depthwise layer behind, else None.  The
+        three kernels' planes are disjoint."""
         if residual is not None or pre is not None or defer_epilogue:
             return None
         if any(dw.k25h_takes(x, self) for dw in self.hand_to):
             return 'k25h'
         if any(dw.k26h_takes(x, self) for dw in self.hand_planes_to):
             return 'k26h'
+        if any(dw.k27h_takes(x, self) for dw in self.hand_tiles_to):
+            return 'k27h'
         return None
 
     def hands_over(self, x, residual=None, pre=None, defer_epilogue=False):
-        """Whether forward(x, ...) leaves `x` untouched to the depthwise layer behind (K25h, K26h): an armed expand,
-        called as the expand of a block is called, and that layer says dw.k25h_takes(x, self) (hand_to) or
-        dw.k26h_takes(x, self) (hand_planes_to)."""
+        """Whether forward(x, ...) leaves `x` untouched to the depthwise layer behind (K25h, K26h, K27h): an armed
+        expand, called as the expand of a block is called, and that layer says dw.k25h_takes(x, self) (hand_to),
+        dw.k26h_takes(x, self) (hand_planes_to) or dw.k27h_takes(x, self) (hand_tiles_to)."""
         return self._handed_kernel(x, residual, pre, defer_epilogue) is not None
 
     def path(self, x, residual=None, pre=None, defer_epilogue=False):
         """Which path forward(x, residual, pre=pre, defer_epilogue=defer_epilogue) runs, as last_path will say it:
-        'k25h' / 'k26h' where an armed expand hands `x` over, else the kernel_for(x) if its epilogue can add `residual` ('_gate'
+        'k25h' / 'k26h' / 'k27h' where an armed expand hands `x` over, else the kernel_for(x) if its epilogue can add `residual` ('_gate'
         behind it where the squeeze-excite block in front handed the gate of this very `x` over), 'library' otherwise.
         `x` as it enters the convolution: the first convolution of a 16-bit copy casts before it asks."""
         handed = self._handed_kernel(x, residual, pre, defer_epilogue)
@@ -644,12 +649,13 @@ class ConvBiasAct(nn.Module):
         """defer_epilogue / pre: between the two layers of an armed FusedMBConv (FusedMBConv._forward_pre) only.
         defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way:
         its "+ bias, activation" is applied here, inside K13 or K20 where one takes `x`, by K10 in front of the library
-        path otherwise.  An armed expand (hand_to, hand_planes_to) whose depthwise layer takes `x` hands it over and returns
-        it untouched: that layer's forward runs both (K25h, K26h)."""
+        path otherwise.  An armed expand (hand_to, hand_planes_to, hand_tiles_to) whose depthwise layer takes `x` hands
+        it over and returns it untouched: that layer's forward runs both (K25h, K26h, K27h)."""
         handed = self._handed_kernel(x, residual, pre, defer_epilogue)
         if handed is not None:
             # decided here, once: the depthwise layer runs this convolution, its bias and its activation itself
-            (self.hand_to if handed == 'k25h' else self.hand_planes_to)[0].hand_over(x, self, handed)
+            {'k25h': self.hand_to, 'k26h': self.hand_planes_to, 'k27h': self.hand_tiles_to}[handed][0].hand_over(
+                x, self, handed)
             self.last_path = handed
             return x
         return self.forward_here(x, residual, defer_epilogue, pre)
@@ -957,7 +963,7 @@ class DepthwiseBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False
         self._mean = None
-        self.last_path = None  # 'k11', 'k15', 'k18', 'k25h', 'k26h' or 'library': what the last forward ran (tests, A/B runs)
+        self.last_path = None  # 'k11', 'k15', 'k18', 'k25h', 'k26h', 'k27h' or 'library': what the last forward ran (tests, A/B runs)
         # fold_batchnorm(block_depthwise=True) sets this on the k = 3, stride-1, padding-1 layers: they run K18 on
         # the planes it takes and K11's block kernel refuses -- the bits of K11's generic kernel, which those planes
         # run on otherwise
@@ -1037,15 +1043,45 @@ class DepthwiseBiasAct(nn.Module):
                 and (K, c.out_channels, H, W) not in DepthwiseBiasAct.k26h_slower
                 and kernels.expand_depthwise16_planes_supported(x, c.weight))
 
+    # K27h (fold_batchnorm(fuse_expand_depthwise_tiles=True)): the class-wide switch, and the (Cin, Cmid, H, W, stride)
+    # of the expand's input where K27h was not ahead of the chain K13h + K11 in every round of tools/expand_dw_ab.py
+    # --kernel k27h: MobileNetV3's 40 -> 240 at 32x32, stride 2 (0.69 - 0.70x; batch 320 at 256 px, f16 and bf16).  Its
+    # 24 -> 72 at 64x64 (1.80 - 1.82x) and 16 -> 64 at 128x128, stride 2 (1.16 - 1.18x) are ahead in every round
+    # (profiles/r23a_expand_dw_ab_k27h.jsonl).  Other networks, planes and batch sizes have not
+    # been timed
+    use_k27h = True
+    k27h_slower = frozenset({(40, 240, 32, 32, 2)})
+
+    def k27h_takes(self, x, expand):
+        """k26h_takes for K27h (expand_dw16_tiles.hip): the same conditions, but this layer emits no mean, has stride 1
+        or 2, and the plane is one of stride 2, or a stride-1 plane that is neither a block-kernel plane (K25h's, or the
+        chain's with other bits) nor one K26h's entry accepts -- so the three kernels never compete for a plane -- and
+        the C entry of K27h accepts the shape."""
+        c = expand.conv
+        if not (DepthwiseBiasAct.use_k27h and not self.emit_mean and self.k == 3 and self.stride in (1, 2)
+                and self.pad == 1 and self.pads is None
+                and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
+                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+            return False
+        held = expand._gate
+        if (held is not None and held[0] is x) or expand.kernel_for(x) != 'k13h':
+            return False
+        B, K, H, W = x.shape
+        if self.stride == 1 and (kernels.k11_takes_block_kernel(H, W)
+                                 or kernels.expand_depthwise16_planes_supported(x, c.weight)):
+            return False
+        return ((K, c.out_channels, H, W, self.stride) not in DepthwiseBiasAct.k27h_slower
+                and kernels.expand_depthwise16_tiles_supported(x, c.weight, self.stride))
+
     def hand_over(self, x, expand, kernel='k25h'):
         """From the armed expand in front: `x` comes WITHOUT that convolution applied; the next forward(x) runs it, on
-        `kernel` ('k25h' / 'k26h') where this layer still takes it."""
+        `kernel` ('k25h' / 'k26h' / 'k27h') where this layer still takes it."""
         self._handed = (x, expand, kernel)
 
     def path(self, x):
         """Which path forward(x) runs on an input that was not handed over, as last_path will say it: 'k18' (an armed
-        3x3 layer), then 'k11' (3x3) or 'k15' (5x5), then 'library' (the torch ops).  ('k25h' / 'k26h': forward, on the
-        input an armed expand handed over.)"""
+        3x3 layer), then 'k11' (3x3) or 'k15' (5x5), then 'library' (the torch ops).  ('k25h' / 'k26h' / 'k27h': forward, on
+        the input an armed expand handed over.)"""
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
         ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
         if not (x.is_cuda and x.is_contiguous() and ow % 4 == 0 and x.dtype in _FLOATS):
@@ -1063,8 +1099,14 @@ class DepthwiseBiasAct(nn.Module):
             expand, kernel = held[1], held[2]
             if kernel == 'k25h':
                 takes, fn = self.k25h_takes(x, expand), kernels.expand_depthwise16
-            else:
+            elif kernel == 'k26h':
                 takes, fn = self.k26h_takes(x, expand), kernels.expand_depthwise16_planes
+            else:
+                takes, fn = self.k27h_takes(x, expand), kernels.expand_depthwise16_tiles
+            if takes and kernel == 'k27h':   # (a layer that emits no mean; the stride is an argument)
+                self.last_path = kernel
+                return fn(x, expand.conv.weight, expand.bias, expand.act_name, self.weight, self.bias, self.act_name,
+                          self.stride)
             if takes:
                 self.last_path = kernel
                 out = fn(x, expand.conv.weight, expand.bias, expand.act_name, self.weight, self.bias, self.act_name,
@@ -1073,7 +1115,7 @@ class DepthwiseBiasAct(nn.Module):
                     return out
                 self._mean = out
                 return out[0]
-            # (the expand asked k25h_takes / k26h_takes before it handed x over; whatever changed since: never
+            # (the expand asked k25h_takes / k26h_takes / k27h_takes before it handed x over; whatever changed since: never
             # un-expanded)
             x = expand.forward_here(x)
         path = self.last_path = self.path(x)
@@ -1286,7 +1328,7 @@ def _arm_deep_projects(folded):
             m.deep_projects = True
 
 
-def _arm_expand_depthwise(folded, field='hand_to'):
+def _arm_expand_depthwise(folded, field='hand_to', strides=(1,)):
     """fuse_expand_depthwise: every plain 1x1 ConvBiasAct that emits no mean and stands directly in front of a 3x3,
     stride-1, padding-1 DepthwiseBiasAct of as many channels without a folded ZeroPad2d -- the expand and depthwise
     layers of the stride-1 MBConv blocks: 28 pairs of EfficientNetV2-S, 59 of -L, 6 of MobileNetV3, none of ResNet-18
@@ -1295,11 +1337,17 @@ def _arm_expand_depthwise(folded, field='hand_to'):
     chain runs everywhere else (24x24, 12x12 and 64x64 planes, the expand shapes of ConvBiasAct.k13h_slower, CPU, ...).
     The stride-2 blocks have their folded ZeroPad2d (an Identity) between the two layers and stay unarmed.
     fuse_expand_depthwise_planes arms the same pairs on `field` 'hand_planes_to' instead, for K26h ('k26h';
-    DepthwiseBiasAct.k26h_takes: the 24x24 and 12x12 planes K25h leaves to the chain)."""
+    DepthwiseBiasAct.k26h_takes: the 24x24 and 12x12 planes K25h leaves to the chain).
+    fuse_expand_depthwise_tiles arms them on 'hand_tiles_to' with `strides` (1, 2): also the stride-2 pairs whose
+    depthwise layer has padding 1, no folded ZeroPad2d and no squeeze-excite block behind it (K27h has no mean), directly
+    behind the expand -- 6 + 2 pairs of MobileNetV3; the stride-2 layers of EfficientNetV2 carry a folded padding or, the
+    one symmetric one of each network, emit the mean, and stay unarmed (28 of -S, 59 of -L) -- for K27h ('k27h';
+    DepthwiseBiasAct.k27h_takes: the large planes of the layers without a squeeze-excite mean)."""
     for _, _, a, b in _adjacent_children(folded):
         expand, dw = _only_layer(a), _only_layer(b)
         if type(expand) is ConvBiasAct and not expand.emit_mean and _plain_1x1(expand.conv) \
-                and isinstance(dw, DepthwiseBiasAct) and dw.k == 3 and dw.stride == 1 and dw.pad == 1 \
+                and isinstance(dw, DepthwiseBiasAct) and dw.k == 3 and dw.stride in strides and dw.pad == 1 \
+                and (dw.stride == 1 or not dw.emit_mean) \
                 and dw.pads is None and dw.weight.shape[0] == expand.conv.out_channels:
             setattr(expand, field, (dw,))
 
@@ -1335,12 +1383,13 @@ _NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
 _OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
                  ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'),
                  ('strided3x3', 'f32'), ('fuse_expand_depthwise', '16bit'),
-                 ('fuse_expand_depthwise_planes', '16bit'))
+                 ('fuse_expand_depthwise_planes', '16bit'), ('fuse_expand_depthwise_tiles', '16bit'))
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                    block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
-                   strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False):
+                   strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False,
+                   fuse_expand_depthwise_tiles=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -1369,8 +1418,11 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     block as one launch, K25h (_arm_expand_depthwise).
     fuse_expand_depthwise_planes=True (needs a 16-bit dtype): the same pairs as one launch on the planes K25h refuses
     (24x24, 12x12: 384 px inputs), K26h (_arm_expand_depthwise on hand_planes_to).
+    fuse_expand_depthwise_tiles=True (needs a 16-bit dtype): the same pairs and the stride-2 pairs without a folded
+    padding as one launch on the large planes of the layers that emit no mean (64x64, 128x128 -> 64x64, 32x32 -> 16x16 of
+    MobileNetV3), K27h (_arm_expand_depthwise on hand_tiles_to).
     The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3; 16-bit:
-    fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise, fuse_expand_depthwise_planes): no two of them arm the same field of the same module, and
+    fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise, fuse_expand_depthwise_planes, fuse_expand_depthwise_tiles): no two of them arm the same field of the same module, and
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
     module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
@@ -1388,7 +1440,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     options = dict(fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
                    deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
                    strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise,
-                   fuse_expand_depthwise_planes=fuse_expand_depthwise_planes)
+                   fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
+                   fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles)
     for option, need in _OPTION_NEEDS:
         met, text = _NEEDS[need]
         if options[option] and not met(fused_epilogue, dtype):
@@ -1418,6 +1471,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         _arm_expand_depthwise(folded)
     if fuse_expand_depthwise_planes:
         _arm_expand_depthwise(folded, 'hand_planes_to')
+    if fuse_expand_depthwise_tiles:
+        _arm_expand_depthwise(folded, 'hand_tiles_to', strides=(1, 2))
     if fuse_stem:
         _fuse_stem(folded)
     return folded

@@ -1097,6 +1097,57 @@ def expand_depthwise16_planes(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean
     return (out, mean) if want_mean else out
 
 
+# K27h: the same pair on large planes, stride 1 or 2, in bands of output rows and without a mean
+# (csrc/expand_dw16_tiles.hip)
+
+def expand_depthwise16_tiles_supported(x, w1, stride=1):
+    """Whether mtr_expand_dw16_tiles takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous,
+    both 16-byte aligned, Cin a multiple of 8, H and W at most 128, fewer than 2^30 planes of output; at stride 1
+    W % 4 == 0, H W % 8 == 0 and a plane K11 does NOT run on its stride-1 block kernel (k11_takes_block_kernel); at
+    stride 2 H even and W % 8 == 0 (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).
+    `w1` is the expand's weight, [Cmid, Cin] or [Cmid, Cin, 1, 1]."""
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
+            or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if w1.numel() != w1.shape[0] * K:
+        return False
+    return _lib.load().mtr_expand_dw16_tiles_lds_bytes(B, K, w1.shape[0], H, W, int(stride)) > 0
+
+
+def expand_depthwise16_tiles(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, out=None):
+    """K27h: y = act2(depthwise_conv3x3(act1(conv1x1(x, w1) + bias1), w_dw, stride, padding 1) + bias_dw) in one launch
+    on the current stream, the expanded activation kept in LDS band by band; no mean.  y [B, Cmid, H / stride,
+    W / stride] has the bits of conv1x1_bias_act16 followed by depthwise3x3_bias_act(.., stride, 1) on a plane K11 runs
+    on its generic kernel (at stride 1 also the bits of depthwise3x3_blocks_bias_act behind conv1x1_bias_act16), the
+    same on every call and graph replay.  What the kernel does not take raises (expand_depthwise16_tiles_supported
+    asks first); there is no fallback in here."""
+    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('expand_depthwise16_tiles: x must be [B, Cin, H, W], NCHW-contiguous')
+    if stride not in (1, 2):
+        raise ValueError(f'expand_depthwise16_tiles: stride must be 1 or 2, got {stride}')
+    B, K, H, W = x.shape
+    Cmid = w1.shape[0]
+    w1 = w1.reshape(Cmid, -1)
+    if w1.shape[1] != K:
+        raise ValueError(f'expand_depthwise16_tiles: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
+    if w1.dtype != x.dtype:
+        raise ValueError(f'expand_depthwise16_tiles: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
+    if w_dw.numel() != Cmid * 9:
+        raise ValueError(f'expand_depthwise16_tiles: the depthwise weight must be [{Cmid}, 3, 3], got '
+                         f'{tuple(w_dw.shape)}')
+    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
+        raise ValueError(f'expand_depthwise16_tiles: biases have {bias1.numel()} and {bias_dw.numel()} elements, '
+                         f'expected {Cmid} each')
+    out = _residual_and_out('expand_depthwise16_tiles', x, (B, Cmid, H // stride, W // stride), None, out)
+    check(_lib.load().mtr_expand_dw16_tiles(
+        _ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
+        _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
+        int(stride), _ptr(out), current_stream_ptr(x.device)), 'mtr_expand_dw16_tiles')
+    return out
+
+
 # K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one
 # launch (csrc/stem_conv.hip)
 

@@ -22,6 +22,14 @@ does the same for fold_batchnorm(fuse_expand_depthwise_planes=True), K26h (kerne
 more arm, 'k18', is K13h + K18 (kernels.depthwise3x3_blocks_bias_act, what block_depthwise=True runs for the pair) and
 is recorded beside the others.  `slower` and the last line are the rule of DepthwiseBiasAct.k26h_slower, against the
 chain; chain_spread is the chain's largest round over its smallest, the noise floor.
+
+    python tools/expand_dw_ab.py --kernel k27h --out OUT.jsonl
+
+is fold_batchnorm(fuse_expand_depthwise_tiles=True), K27h (kernels.expand_depthwise16_tiles), on the three classes of
+MobileNetV3 at batch 320 and 256 px it takes: 24 -> 72 on 64x64 at stride 1 (with the 'k18' arm), 16 -> 64 on 128x128 and
+40 -> 240 on 32x32 at stride 2.  A key carries the stride as a fifth element, as DepthwiseBiasAct.k27h_slower does; the
+byte floor counts x and W1 read once and the (stride-2: four times smaller) y written once.  K27h has one
+workgroup-to-image mapping: no 'plain' / 'xcd' arms.
 """
 import argparse
 import json
@@ -39,11 +47,15 @@ KERNELS = {
     'k26h': dict(option='fuse_expand_depthwise_planes', field='hand_planes_to', switch='use_k26h',
                  slower='k26h_slower', takes='k26h_takes', fn='expand_depthwise16_planes',
                  lds='mtr_expand_dw16_planes_lds_bytes', workloads=[('effnetv2-l', 32, 384), ('effnetv2-s', 64, 384)]),
+    'k27h': dict(option='fuse_expand_depthwise_tiles', field='hand_tiles_to', switch='use_k27h',
+                 slower='k27h_slower', takes='k27h_takes', fn='expand_depthwise16_tiles',
+                 lds='mtr_expand_dw16_tiles_lds_bytes', workloads=[('mobilenetv3', 320, 256)], strided=True),
 }
 
 
 def armed_pairs(net, res, cfg):
-    """{(Cin, Cmid, H, W): [(expand, depthwise), ...]} of the armed pairs of `net` at `res` px."""
+    """{(Cin, Cmid, H, W): [(expand, depthwise), ...]} of the armed pairs of `net` at `res` px (cfg['strided']: the
+    depthwise layer's stride as a fifth element of the key)."""
     import torch
     from metrabs_amd import backbones
     out = {}
@@ -52,8 +64,9 @@ def armed_pairs(net, res, cfg):
         if isinstance(m, backbones.ConvBiasAct) and getattr(m, cfg['field']):
             def hook(mod, args):
                 x = args[0]
+                dw = getattr(mod, cfg['field'])[0]
                 key = (mod.conv.in_channels, mod.conv.out_channels, x.shape[2], x.shape[3])
-                out.setdefault(key, []).append((mod, getattr(mod, cfg['field'])[0]))
+                out.setdefault(key + ((dw.stride,) if cfg.get('strided') else ()), []).append((mod, dw))
             hooks.append(m.register_forward_pre_hook(hook))
     setattr(backbones.DepthwiseBiasAct, cfg['switch'], False)
     try:
@@ -114,8 +127,11 @@ def main():
                                            **{cfg['option']: True}).cuda()
             g = torch.Generator(device='cuda').manual_seed(0)
             for key, pairs in armed_pairs(net, res, cfg).items():
-                Cin, Cmid, H, W = key
+                Cin, Cmid, H, W = key[:4]
                 e, d = pairs[0]
+                stride = d.stride
+                if kn == 'k27h' and (stride == 1 and kernels.k11_takes_block_kernel(H, W) or d.emit_mean):
+                    continue   # (the 16x16 pairs: not K27h's planes)
                 x = torch.randn(B, Cin, H, W, device='cuda', generator=g).to(dt)
 
                 def chain():
@@ -138,14 +154,16 @@ def main():
                     supported = getattr(d, cfg['takes'])(x, e)
                     arms = {'chain': chain}
                     equal = None
-                    if kn == 'k26h':
+                    if kn == 'k26h' or (kn == 'k27h' and stride == 1):
                         arms['k18'] = k18
                     if supported:
                         c = fused()
                         assert (e.last_path, d.last_path) == (kn, kn)
                         torch.cuda.synchronize()
                         equal = bool(torch.equal(a, c))
-                        arms.update({kn: fused, 'plain': mapped('plain'), 'xcd': mapped('xcd')})
+                        arms[kn] = fused
+                        if kn != 'k27h':
+                            arms.update(plain=mapped('plain'), xcd=mapped('xcd'))
                     for _ in range(3):
                         for fn in arms.values():
                             fn()
@@ -158,11 +176,11 @@ def main():
                         for n, gr in graphs.items():
                             t[n].append(timed(gr))
                     del graphs
-                byts = 2 * (B * H * W * (Cin + Cmid) + Cmid * Cin)
+                byts = 2 * (B * H * W * Cin + B * (H // stride) * (W // stride) * Cmid + Cmid * Cin)
                 mid_mb = 2 * B * H * W * Cmid / 1e6
                 floor = byts / (HBM_TBS * 1e12) * 1e6
                 row = dict(backbone=backbone, batch=B, res=res, dtype=dname, cin=Cin, cmid=Cmid, hw=f'{H}x{W}',
-                           act=e.act_name, mean=d.emit_mean, layers=len(pairs), chain_expand=chain_paths[0],
+                           act=e.act_name, stride=stride, mean=d.emit_mean, layers=len(pairs), chain_expand=chain_paths[0],
                            chain_depthwise=chain_paths[1], mbytes=round(byts / 1e6, 1), mid_mbytes=round(mid_mb, 1),
                            chain_us=round(med(t['chain']), 2), chain_us_rounds=[round(v, 2) for v in t['chain']],
                            listed=key in listed, **{kn + '_us': None})
@@ -173,13 +191,15 @@ def main():
                     tk = med(t[kn])
                     ahead_every_round = all(n < o for n, o in zip(t[kn], t['chain']))
                     row.update({kn + '_us': round(tk, 2), kn + '_us_rounds': [round(v, 2) for v in t[kn]]})
+                    if 'plain' in t:
+                        row.update(plain_us_rounds=[round(v, 2) for v in t['plain']],
+                                   xcd_us_rounds=[round(v, 2) for v in t['xcd']])
                     row.update(
-                               plain_us_rounds=[round(v, 2) for v in t['plain']],
-                               xcd_us_rounds=[round(v, 2) for v in t['xcd']],
                                speedup=round(med(t['chain']) / tk, 3), byte_floor_us=round(floor, 2),
                                share_of_byte_floor=round(floor / tk, 3), equal_bits=equal,
                                slower=not ahead_every_round,
-                               lds_bytes=int(getattr(kernels._lib.load(), cfg['lds'])(B, Cin, Cmid, H, W)))
+                               lds_bytes=int(getattr(kernels._lib.load(), cfg['lds'])(
+                                   B, Cin, Cmid, H, W, *((stride,) if cfg.get('strided') else ()))))
                     if not ahead_every_round:
                         losers.add(key)
                 rows.append(row)
