@@ -451,6 +451,21 @@ def _derived_weight(slot, w, make):
     return slot if slot is not None and slot[0] == key else (key, make(w))
 
 
+# The kernels that run the 1x1 expand of an MBConv block and the depthwise 3x3 layer behind it as one launch, in the
+# order an armed expand asks them (their planes are disjoint).  Per kernel, which is also its last_path: the
+# fold_batchnorm option that arms the pairs, the ConvBiasAct field it sets on the expand (a field of its own per option,
+# so no two options arm one field), DepthwiseBiasAct's question, class-wide switch and list of slower shapes, the wrapper
+# in kernels, and whether the call passes the layer's stride (else want_mean).  THE place that says which goes with which.
+EXPAND_DW_KERNELS = {
+    'k25h': dict(option='fuse_expand_depthwise', field='hand_to', takes='k25h_takes', switch='use_k25h',
+                 slower='k25h_slower', fn='expand_depthwise16', strided=False),
+    'k26h': dict(option='fuse_expand_depthwise_planes', field='hand_planes_to', takes='k26h_takes',
+                 switch='use_k26h', slower='k26h_slower', fn='expand_depthwise16_planes', strided=False),
+    'k27h': dict(option='fuse_expand_depthwise_tiles', field='hand_tiles_to', takes='k27h_takes',
+                 switch='use_k27h', slower='k27h_slower', fn='expand_depthwise16_tiles', strided=True),
+}
+
+
 class ConvBiasAct(nn.Module):
     """A folded conv + BN (+ activation): the convolution without its bias (MIOpen / rocBLAS), then
     "+ bias[c]" and the activation as ONE in-place pass (kernels.bias_act_, K10) instead of the two
@@ -592,12 +607,9 @@ class ConvBiasAct(nn.Module):
         three kernels' planes are disjoint."""
         if residual is not None or pre is not None or defer_epilogue:
             return None
-        if any(dw.k25h_takes(x, self) for dw in self.hand_to):
-            return 'k25h'
-        if any(dw.k26h_takes(x, self) for dw in self.hand_planes_to):
-            return 'k26h'
-        if any(dw.k27h_takes(x, self) for dw in self.hand_tiles_to):
-            return 'k27h'
+        for kernel, cfg in EXPAND_DW_KERNELS.items():
+            if any(getattr(dw, cfg['takes'])(x, self) for dw in getattr(self, cfg['field'])):
+                return kernel
         return None
 
     def hands_over(self, x, residual=None, pre=None, defer_epilogue=False):
@@ -654,8 +666,7 @@ class ConvBiasAct(nn.Module):
         handed = self._handed_kernel(x, residual, pre, defer_epilogue)
         if handed is not None:
             # decided here, once: the depthwise layer runs this convolution, its bias and its activation itself
-            {'k25h': self.hand_to, 'k26h': self.hand_planes_to, 'k27h': self.hand_tiles_to}[handed][0].hand_over(
-                x, self, handed)
+            getattr(self, EXPAND_DW_KERNELS[handed]['field'])[0].hand_over(x, self, handed)
             self.last_path = handed
             return x
         return self.forward_here(x, residual, defer_epilogue, pre)
@@ -999,21 +1010,27 @@ class DepthwiseBiasAct(nn.Module):
                              (112, 672, 16, 16)})
     _handed = None
 
+    def _expand_dw_candidate(self, x, expand, strides, switch):
+        """What k25h_takes, k26h_takes and k27h_takes ask first: the class-wide `switch` is on, this is a 3x3 padding-1
+        layer of a stride in `strides` without a folded ZeroPad2d, an inference call on both weights, a CUDA
+        NCHW-contiguous input of the copy's dtype that `expand` would run on K13h with no gate held."""
+        c = expand.conv
+        if not (getattr(DepthwiseBiasAct, switch) and self.k == 3 and self.stride in strides and self.pad == 1
+                and self.pads is None and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
+                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+            return False
+        held = expand._gate
+        return not (held is not None and held[0] is x) and expand.kernel_for(x) == 'k13h'
+
     def k25h_takes(self, x, expand):
         """Whether this layer runs `expand` (the armed 1x1 ConvBiasAct in front) and itself on `x`, the expand's input,
         as one launch (K25h, expand_dw16.hip): a 3x3 stride-1 padding-1 layer without a folded ZeroPad2d, an inference
         call on both weights, a CUDA NCHW-contiguous input of the copy's dtype that the expand would run on K13h with
         no gate held, a plane K11 runs on its block kernel, a shape the C entry accepts and that is not listed as
         slower.  Everything else runs the chain: today's branch, today's bits."""
-        c = expand.conv
-        if not (DepthwiseBiasAct.use_k25h and self.k == 3 and self.stride == 1 and self.pad == 1 and self.pads is None
-                and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
-                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+        if not self._expand_dw_candidate(x, expand, (1,), 'use_k25h'):
             return False
-        held = expand._gate
-        if (held is not None and held[0] is x) or expand.kernel_for(x) != 'k13h':
-            return False
-        B, K, H, W = x.shape
+        c, (B, K, H, W) = expand.conv, x.shape
         return (kernels.k11_takes_block_kernel(H, W)
                 and (K, c.out_channels, H, W) not in DepthwiseBiasAct.k25h_slower
                 and kernels.expand_depthwise16_supported(x, c.weight))
@@ -1030,15 +1047,9 @@ class DepthwiseBiasAct(nn.Module):
     def k26h_takes(self, x, expand):
         """k25h_takes for K26h (expand_dw16_planes.hip): the same conditions, but the plane is one K11 does NOT run on
         its block kernel -- 24x24, 12x12 -- and the C entry of K26h accepts the shape."""
-        c = expand.conv
-        if not (DepthwiseBiasAct.use_k26h and self.k == 3 and self.stride == 1 and self.pad == 1 and self.pads is None
-                and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
-                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+        if not self._expand_dw_candidate(x, expand, (1,), 'use_k26h'):
             return False
-        held = expand._gate
-        if (held is not None and held[0] is x) or expand.kernel_for(x) != 'k13h':
-            return False
-        B, K, H, W = x.shape
+        c, (B, K, H, W) = expand.conv, x.shape
         return (not kernels.k11_takes_block_kernel(H, W)
                 and (K, c.out_channels, H, W) not in DepthwiseBiasAct.k26h_slower
                 and kernels.expand_depthwise16_planes_supported(x, c.weight))
@@ -1057,16 +1068,9 @@ class DepthwiseBiasAct(nn.Module):
         or 2, and the plane is one of stride 2, or a stride-1 plane that is neither a block-kernel plane (K25h's, or the
         chain's with other bits) nor one K26h's entry accepts -- so the three kernels never compete for a plane -- and
         the C entry of K27h accepts the shape."""
-        c = expand.conv
-        if not (DepthwiseBiasAct.use_k27h and not self.emit_mean and self.k == 3 and self.stride in (1, 2)
-                and self.pad == 1 and self.pads is None
-                and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
-                and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
+        if self.emit_mean or not self._expand_dw_candidate(x, expand, (1, 2), 'use_k27h'):
             return False
-        held = expand._gate
-        if (held is not None and held[0] is x) or expand.kernel_for(x) != 'k13h':
-            return False
-        B, K, H, W = x.shape
+        c, (B, K, H, W) = expand.conv, x.shape
         if self.stride == 1 and (kernels.k11_takes_block_kernel(H, W)
                                  or kernels.expand_depthwise16_planes_supported(x, c.weight)):
             return False
@@ -1097,20 +1101,13 @@ class DepthwiseBiasAct(nn.Module):
         held, self._handed = self._handed, None
         if held is not None and held[0] is x:  # the expand in front left its convolution to this module
             expand, kernel = held[1], held[2]
-            if kernel == 'k25h':
-                takes, fn = self.k25h_takes(x, expand), kernels.expand_depthwise16
-            elif kernel == 'k26h':
-                takes, fn = self.k26h_takes(x, expand), kernels.expand_depthwise16_planes
-            else:
-                takes, fn = self.k27h_takes(x, expand), kernels.expand_depthwise16_tiles
-            if takes and kernel == 'k27h':   # (a layer that emits no mean; the stride is an argument)
+            cfg = EXPAND_DW_KERNELS[kernel]
+            if getattr(self, cfg['takes'])(x, expand):
                 self.last_path = kernel
-                return fn(x, expand.conv.weight, expand.bias, expand.act_name, self.weight, self.bias, self.act_name,
-                          self.stride)
-            if takes:
-                self.last_path = kernel
-                out = fn(x, expand.conv.weight, expand.bias, expand.act_name, self.weight, self.bias, self.act_name,
-                         want_mean=self.emit_mean)
+                # (a strided kernel's layer emits no mean; the stride is an argument)
+                extra = dict(stride=self.stride) if cfg['strided'] else dict(want_mean=self.emit_mean)
+                out = getattr(kernels, cfg['fn'])(x, expand.conv.weight, expand.bias, expand.act_name, self.weight,
+                                                  self.bias, self.act_name, **extra)
                 if not self.emit_mean:
                     return out
                 self._mean = out

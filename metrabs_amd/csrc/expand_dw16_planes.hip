@@ -1,27 +1,16 @@
-// K26h: K25h's function (expand_dw16.hip: the 1x1 expand convolution of an MBConv block and the depthwise 3x3 stride-1
-// convolution behind it, f16 / bf16, ONE launch, the expanded activation kept in LDS) on the planes K25h refuses
-// because K11 runs them on its GENERIC kernel: 24x24 and 12x12 of the EfficientNetV2 family at 384 px, and every
-// other plane up to 576 positions whose W / 4 or H / 4 is no power of two.
+// K26h: the function of expand_dw16.h, with the mean, on the planes K25h (expand_dw16.hip) refuses because K11 runs
+// them on its GENERIC kernel (depthwise3x3_kernel): 24x24 and 12x12 of the EfficientNetV2 family at 384 px, and every
+// other plane up to 576 positions whose W / 4 or H / 4 is no power of two.  The bits of K13h followed by K11's generic
+// kernel are also the bits of K13h + K18 (depthwise3x3_blocks.hip).
 //
 // Not part of the reference's hot path (like K10 - K25h): backbones.fold_batchnorm(dtype=f16 / bf16,
-// fuse_expand_depthwise_planes=True).  Per image b, K25h's three formulas:
+// fuse_expand_depthwise_planes=True).  A workgroup of four waves owns CM expanded channels of one image over the whole
+// plane:
 //
-//   mid[b, c, p] = rnd16(act1(bias1[c] + sum_k W1[c, k] * x[b, k, p]))                                  c < Cmid
-//   y[b, c, p]   = rnd16(act2(bias2[c] + sum_{ky, kx} Wd[c, ky, kx] * mid[b, c, p + (ky - 1, kx - 1)]))
-//   mean[b, c]   = (1 / HW) * sum_p f32(y[b, c, p])                                                    (optional)
-//
-// with the BITS of conv1x1_16_kernel (K13h) followed by depthwise3x3_kernel (K11's generic kernel) -- which are also
-// the bits of K13h + K18 (depthwise3x3_blocks.hip).  A workgroup of four waves owns CM expanded channels of one image
-// over the whole plane:
-//
-//   phase 1  K13h's GEMM exactly as K25h runs it (16-k steps at k = 0, 16, ... on v_mfma_f32_32x32x16_{f16,bf16}, k
-//            past Cin and positions past H W zero-filled, the X^T image in two LDS buffers in k-tiles of 32, the weight
-//            fragments from global memory one k-tile ahead; bias + activation in f32, one plain-cast rounding behind
-//            `settled`).  K13h's bits do not depend on the tile, so the plane is cut into ceil(H W / 32) position tiles
-//            of any count: FN per wave, WN waves along the positions (the tiles past the plane compute zeros and store
-//            nothing).  A loader thread owns up to three units of 4 k x 8 positions.
-//   between  the same LDS becomes the slice's image [c][H + 2][W + 8] inside a zero ring (image column j at index
-//            j + 4), zeroed first; the (row, column) of a position comes from a division by W.
+//   phase 1  edw_gemm_plane over ceil(H W / 32) position tiles of any count: FN per wave, WN waves along the positions
+//            (the tiles past the plane compute zeros and store nothing); a loader thread owns up to three units.  The
+//            (row, column) of a position comes from a division by W.
+//   between  the slice's image [c][H + 2][W + 8] (image column j at index j + 4).
 //   phase 2  depthwise3x3_kernel's mapping and arithmetic: lpp = min(64, next power of two >= groups) lanes per
 //            channel (groups = H W / 4 groups of four horizontally adjacent outputs), 64 / lpp channels per wave, lane
 //            `sub` walks the groups sub, sub + 64, ...  Per output the accumulator starts at 0, nine fmaf with ky outer
@@ -29,37 +18,10 @@
 //            group summed left to right from 0.0f, the lane's groups added in ascending order from 0.0f, the xor
 //            butterfly lpp / 2 .. 1, times 1.0f / (float)(H W).  No LDS for partial sums.
 //
-// The workgroup-to-image mapping is K25h's (by default the chunks of one image on one XCD; the bits do not depend on
-// it).  No atomics, no split-K, no workspace: the same inputs give the same bits.
-#include "common.h"
+// The workgroup-to-image mapping is edw_image_chunk's, as K25h's.
+#include "expand_dw16.h"
 
 namespace mtr {
-
-typedef float edp_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned short edp_u16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT> struct EdpBits;
-template <> struct EdpBits<MTR_F16> {
-  typedef __half T;  // K11's element type: phase 2 rounds and widens exactly as depthwise.hip does
-  typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-  static __device__ __forceinline__ edp_f32x16 mfma(uint4 a, uint4 b, edp_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
-  }
-};
-template <> struct EdpBits<MTR_BF16> {
-  typedef __hip_bfloat16 T;
-  typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
-  static __device__ __forceinline__ edp_f32x16 mfma(uint4 a, uint4 b, edp_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
-  }
-};
-
-constexpr int kEdpBK = 32;               // k-tile of the X^T image
-constexpr int kEdpLDK = kEdpBK + 8;      // its row (one position), padded like K13h's
-constexpr int kEdpColPad = 4;            // image column j of the slice's image sits at index j + 4
-constexpr size_t kEdpMaxLds = 160 * 1024;
 
 struct EdpGeo {
   int Cin, Cmid, H, W, HW;
@@ -88,146 +50,36 @@ __global__ __launch_bounds__(256) void expand_dw16_planes_kernel(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ w1, const float* __restrict__ bias1,
     const float* __restrict__ wd, const float* __restrict__ bias2, unsigned short* __restrict__ y,
     float* __restrict__ row_mean, EdpGeo g, int B, int act1, int act2) {
-  using Hh = EdpBits<DT>;
+  using Hh = EdwBits<DT>;
   using T = typename Hh::T;
   using Tl = EdpTiles<FN, WN>;
   constexpr int WM = Tl::WM, CM = Tl::CM, BN = Tl::BN;
-  constexpr int BK = kEdpBK, LDK = kEdpLDK, KS = BK / 16;
-  constexpr int UNITS = (BK / 4) * (BN / 8);  // loader units of 4 k x 8 positions
-  constexpr int NU = (UNITS + 255) / 256;     // units per loader thread
   extern __shared__ __attribute__((aligned(16))) unsigned short edp_lds[];
   unsigned short* xs = edp_lds;  // phase 1: [2][BN * LDK], the X^T image of a k-tile
   unsigned short* ms = edp_lds;  // afterwards: [CM][H + 2][LW], the slice of the expanded activation
 
   int b, chunk;
-  if (g.xcd_map) {
-    const int q = (int)blockIdx.x >> 3;
-    b = (q / g.chunks) * 8 + ((int)blockIdx.x & 7);
-    chunk = q % g.chunks;
-    if (b >= B) return;  // (the whole workgroup, before any barrier)
-  } else {
-    b = (int)blockIdx.x / g.chunks;
-    chunk = (int)blockIdx.x % g.chunks;
-  }
+  edw_image_chunk(g.xcd_map, g.chunks, b, chunk);
+  if (b >= B) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave % WM, wn = wave / WM;
   const int r = lane & 31, h = lane >> 5;
   const int M = g.Cmid, K = g.Cin, HW = g.HW;
   const int m0 = chunk * CM;
 
-  // ---- phase 1: conv1x1_16_kernel's loop over one image, columns 0 .. HW - 1 (past HW: zero-filled, never written)
-  const unsigned short* xb = x + (long long)b * K * HW;
-  edp_u16x8 xr[NU][4];
-  auto load_x = [&](int k0) {
-#pragma unroll
-    for (int n = 0; n < NU; ++n) {
-      const int u = tid + 256 * n;
-      const int p8 = u % (BN / 8), k4 = u / (BN / 8);
-      const bool on = u < UNITS && 8 * p8 < HW;  // (H W % 8 == 0: a unit is inside the plane or past it)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int k = k0 + 4 * k4 + i;
-        edp_u16x8 t = (edp_u16x8)0;
-        if (on && k < K)
-          t = __builtin_bit_cast(edp_u16x8, *reinterpret_cast<const uint4*>(xb + (long long)k * HW + 8 * p8));
-        xr[n][i] = t;
-      }
-    }
-  };
-  auto store_x = [&](int buf) {  // 4 k-rows x 8 positions -> 8 positions x 4 k of the X^T image
-#pragma unroll
-    for (int n = 0; n < NU; ++n) {
-      const int u = tid + 256 * n;
-      const int p8 = u % (BN / 8), k4 = u / (BN / 8);
-      if (u < UNITS) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          uint2 v;
-          v.x = (unsigned)xr[n][0][j] | ((unsigned)xr[n][1][j] << 16);
-          v.y = (unsigned)xr[n][2][j] | ((unsigned)xr[n][3][j] << 16);
-          *reinterpret_cast<uint2*>(&xs[buf * (BN * LDK) + (8 * p8 + j) * LDK + 4 * k4]) = v;
-        }
-      }
-    }
-  };
-  // this lane's weight fragments: row m0 + 32 wm + r, k 16 s + 8 h .. + 7 of each k-tile
-  const int mrow = m0 + wm * 32 + r;
-  auto load_w = [&](uint4 (&wr)[KS], int k0) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int k = k0 + 16 * s + 8 * h;
-      uint4 t = make_uint4(0u, 0u, 0u, 0u);
-      if (mrow < M && k < K) t = *reinterpret_cast<const uint4*>(w1 + (long long)mrow * K + k);
-      wr[s] = t;
-    }
-  };
+  // ---- phase 1; this lane's channel: cl of the slice
+  const int cl = wm * 32 + r;
+  const EdwPlaneTiles tiles = {wn * (32 * FN)};
+  edw_f32x16 acc[1][FN];
+  edw_gemm_plane<Hh, BN>(acc, xs, x + (long long)b * K * HW, w1, m0 + cl, M, K, HW, tid, tiles);
 
-  edp_f32x16 acc[FN];
-#pragma unroll
-  for (int j = 0; j < FN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[j][e] = 0.0f;
-
-  uint4 wc[KS], wnx[KS];
-  const int n_tiles = (K + BK - 1) / BK;
-  load_x(0);
-  load_w(wc, 0);
-  store_x(0);
+  // ---- the X^T buffers are free: the slice's image (CM % 64 == 0, LW % 4 == 0: whole 16-byte groups)
+  edw_zero_image(ms, CM * g.plane, tid);
   __syncthreads();
-  for (int t = 0; t < n_tiles; ++t) {
-    const int buf = t & 1;
-    if (t + 1 < n_tiles) {  // in flight during this tile's MFMAs
-      load_x((t + 1) * BK);
-      load_w(wnx, (t + 1) * BK);
-    }
-    const unsigned short* xa = &xs[buf * (BN * LDK) + (wn * (32 * FN) + r) * LDK + 8 * h];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const uint4 a = *reinterpret_cast<const uint4*>(xa + (32 * j) * LDK + 16 * s);
-        acc[j] = Hh::mfma(a, wc[s], acc[j]);
-      }
-    }
-    if (t + 1 < n_tiles) {
-      store_x(buf ^ 1);  // the other buffer: last read before the previous barrier
-#pragma unroll
-      for (int s = 0; s < KS; ++s) wc[s] = wnx[s];
-    }
-    __syncthreads();
-  }
-
-  // ---- the X^T buffers are free (the barrier above): zero the slice's image, ring and dead channels included
-  {
-    const int n16 = (CM * g.plane) >> 3;  // (CM % 64 == 0, LW % 4 == 0: whole 16-byte groups)
-    for (int i = tid; i < n16; i += 256) reinterpret_cast<uint4*>(ms)[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  // K13h's epilogue: the lane holds channel .. + r, positions 8 q + 4 h + 0 .. 3 of each 32-position tile (one row of
-  // the plane: W % 4 == 0)
-  auto epilogue = [&](auto tag) {
-    constexpr int ACT = decltype(tag)::value;
-    const int cl = wm * 32 + r;
-    if (m0 + cl >= M) return;
-    const float bm = bias1[m0 + cl];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int p = wn * (32 * FN) + 32 * j + 8 * q + 4 * h;
-        if (p >= HW) continue;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = settled(activate<ACT>(acc[j][4 * q + e] + bm));
-        uint2 o;
-        o.x = (unsigned)Hh::rnd(v[0]) | ((unsigned)Hh::rnd(v[1]) << 16);
-        o.y = (unsigned)Hh::rnd(v[2]) | ((unsigned)Hh::rnd(v[3]) << 16);
-        const int row = (int)fastdiv((unsigned)p, g.d_w), col = p - row * g.W;
-        *reinterpret_cast<uint2*>(&ms[cl * g.plane + (row + 1) * g.LW + kEdpColPad + col]) = o;
-      }
-    }
-  };
-  with_act(act1, epilogue);
+  edw_store_expanded<Hh>(
+      acc, act1, bias1, m0, M, cl, h, tiles, 0, 0, HW,
+      [&](int p, int& row, int& col) { row = (int)fastdiv((unsigned)p, g.d_w), col = p - row * g.W; },
+      EdwImage{ms, g.plane, g.LW, -1, kEdwColPad});
   __syncthreads();
 
   // ---- phase 2: depthwise3x3_kernel's lanes and arithmetic, the taps from LDS (the ring is zero: no masks)
@@ -262,12 +114,12 @@ __global__ __launch_bounds__(256) void expand_dw16_planes_kernel(
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
           const unsigned short* row = mp + ky * g.LW;
-          const V4 mid4 = *reinterpret_cast<const V4*>(row + kEdpColPad);
+          const V4 mid4 = *reinterpret_cast<const V4*>(row + kEdwColPad);
           float in[6];
-          in[0] = to_f32(__builtin_bit_cast(T, row[kEdpColPad - 1]));
+          in[0] = to_f32(__builtin_bit_cast(T, row[kEdwColPad - 1]));
 #pragma unroll
           for (int j = 0; j < 4; ++j) in[1 + j] = to_f32(mid4.v[j]);
-          in[5] = to_f32(__builtin_bit_cast(T, row[kEdpColPad + 4]));
+          in[5] = to_f32(__builtin_bit_cast(T, row[kEdwColPad + 4]));
 #pragma unroll
           for (int o = 0; o < 4; ++o)
 #pragma unroll
@@ -293,31 +145,18 @@ __global__ __launch_bounds__(256) void expand_dw16_planes_kernel(
   with_act(act2, depthwise);
 }
 
-static int edp_ilog2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
-// launch_depthwise's condition for K11's stride-1 block kernel (depthwise.hip), restated for a 16-byte aligned x
-static bool edp_k11_block_plane(int H, int W) {
-  if (H % 4 || W % 4) return false;
-  const int tw = edp_ilog2_exact(W / 4), th = edp_ilog2_exact(H / 4);
-  return tw >= 0 && tw <= 4 && th >= 0 && tw + th <= 6;
-}
-
 // the shape rules of the entry (MTR_E_SHAPE: the caller keeps the two-kernel chain); fills g
 static int expand_dw16_planes_shape(EdpGeo& g, long long B, int Cin, int Cmid, int H, int W) {
   if (B < 0 || Cin <= 0 || Cmid <= 0 || H <= 0 || W <= 0) return MTR_E_SHAPE;
   if (Cin % 8 || W % 4) return MTR_E_SHAPE;  // 16-byte groups of k; whole groups of four outputs
   if (H > 32 || W > 32 || H * W > 576 || (H * W) % 8) return MTR_E_SHAPE;  // 16-byte groups of positions
-  if (edp_k11_block_plane(H, W)) return MTR_E_SHAPE;  // (K11's block kernel: other bits; K25h's planes among them)
+  if (edw_k11_block_plane(H, W)) return MTR_E_SHAPE;  // (K11's block kernel: other bits; K25h's planes among them)
   if (B * Cmid >= (1LL << 30)) return MTR_E_SHAPE;  // (the generic kernel's own limit)
   const int HW = H * W;
   if ((long long)Cin * HW > 0x7fffffffLL || (long long)Cmid * 9 > 0x7fffffffLL) return MTR_E_SHAPE;
   g = EdpGeo{};
   g.Cin = Cin, g.Cmid = Cmid, g.H = H, g.W = W, g.HW = HW;
-  g.LW = W + 2 * kEdpColPad, g.plane = (H + 2) * g.LW;
+  g.LW = W + 2 * kEdwColPad, g.plane = (H + 2) * g.LW;
   g.xcd_map = 1;
   g.groups = HW / 4;
   g.lpp_log2 = 0;
@@ -329,45 +168,23 @@ static int expand_dw16_planes_shape(EdpGeo& g, long long B, int Cin, int Cmid, i
   return MTR_OK;
 }
 
-struct EdpArgs {
-  const void *x, *w1;
-  const float *bias1, *wd, *bias2;
-  void* y;
-  float* row_mean;
-  int act1, act2;
-  long long B;
-  hipStream_t stream;
-};
-
-// y == NULL: the shape query (mtr_expand_dw16_planes_lds_bytes), -> the bytes of LDS, no launch
 template <int DT, int FN, int WN>
-static int launch_expand_dw16_planes_cfg(const EdpArgs& a, EdpGeo g) {
+static int launch_expand_dw16_planes_cfg(const EdwArgs& a, EdpGeo g) {
   using Tl = EdpTiles<FN, WN>;
   g.chunks = (g.Cmid + Tl::CM - 1) / Tl::CM;
-  const size_t xs_bytes = (size_t)2 * Tl::BN * kEdpLDK * sizeof(unsigned short);
-  const size_t ms_bytes = (size_t)Tl::CM * g.plane * sizeof(unsigned short);
-  const size_t lds = xs_bytes > ms_bytes ? xs_bytes : ms_bytes;
-  if (lds > kEdpMaxLds) return MTR_E_SHAPE;
-  const long long images = g.xcd_map ? (a.B + 7) / 8 * 8 : a.B;
-  const long long gx = images * g.chunks;
-  if (gx > 0x7fffffffLL) return MTR_E_SHAPE;
-  if (!a.y) return (int)lds;
   auto kern = expand_dw16_planes_kernel<DT, FN, WN>;
-  if (lds > 64 * 1024) {
-    const int e = allow_dynamic_lds((const void*)kern, kEdpMaxLds);
-    if (e != MTR_OK) return e;
-  }
-  MTR_CLEAR_STALE();
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, a.stream, (const unsigned short*)a.x,
-                     (const unsigned short*)a.w1, a.bias1, a.wd, a.bias2, (unsigned short*)a.y, a.row_mean, g,
-                     (int)a.B, a.act1, a.act2);
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return edw_launch((const void*)kern, a, (size_t)2 * Tl::BN * kEdwLDK * sizeof(unsigned short),
+                    (size_t)Tl::CM * g.plane * sizeof(unsigned short),
+                    (g.xcd_map ? (a.B + 7) / 8 * 8 : a.B) * g.chunks, [&](dim3 grid, size_t lds) {
+                      hipLaunchKernelGGL(kern, grid, dim3(256), lds, a.stream, (const unsigned short*)a.x,
+                                         (const unsigned short*)a.w1, a.bias1, a.wd, a.bias2, (unsigned short*)a.y,
+                                         a.row_mean, g, (int)a.B, a.act1, a.act2);
+                    });
 }
 
 // the only place that maps a plane to template parameters
 template <int DT>
-static int launch_expand_dw16_planes(const EdpArgs& a, const EdpGeo& g) {
+static int launch_expand_dw16_planes(const EdwArgs& a, const EdpGeo& g) {
   const int npt = (g.HW + 31) / 32;
   if (npt <= 5) return launch_expand_dw16_planes_cfg<DT, 5, 1>(a, g);
   if (npt <= 10) return launch_expand_dw16_planes_cfg<DT, 5, 2>(a, g);
@@ -380,7 +197,7 @@ extern "C" size_t mtr_expand_dw16_planes_lds_bytes(long long B, int Cin, int Cmi
   mtr::EdpGeo g;
   if (B <= 0 || mtr::expand_dw16_planes_shape(g, B, Cin, Cmid, H, W) != MTR_OK) return 0;
   // (the tile and LDS rules do not depend on the dtype)
-  mtr::EdpArgs a = {};
+  mtr::EdwArgs a = {};
   a.B = B;
   const int n = mtr::launch_expand_dw16_planes<MTR_F16>(a, g);
   return n > 0 ? (size_t)n : 0;
@@ -390,29 +207,18 @@ extern "C" int mtr_expand_dw16_planes_opts(const void* x, int dtype, const void*
                                            int act1_code, const float* w_dw, const float* bias_dw, int act2_code,
                                            long long B, int Cin, int Cmid, int H, int W, void* y, float* row_mean,
                                            mtr_stream_t stream, int mapping) {
-  if (!x || !w1 || !bias1 || !w_dw || !bias_dw || !y) return MTR_E_NULL;
-  if (dtype != MTR_F16 && dtype != MTR_BF16) return MTR_E_DTYPE;
+  const mtr::EdwArgs a = {x, w1, bias1, w_dw, bias_dw, y, row_mean, act1_code, act2_code, B, (hipStream_t)stream};
   mtr::EdpGeo g;
-  const int e = mtr::expand_dw16_planes_shape(g, B, Cin, Cmid, H, W);
+  const int e = mtr::edw_check(a, dtype, Cin, Cmid, mapping, [&](int& hw_in, int& hw_out) {
+    const int es = mtr::expand_dw16_planes_shape(g, B, Cin, Cmid, H, W);
+    if (es == MTR_OK) hw_in = hw_out = g.HW;
+    return es;
+  });
   if (e != MTR_OK) return e;
-  if (act1_code < mtr::kActNone || act1_code > mtr::kActHardswish || act2_code < mtr::kActNone ||
-      act2_code > mtr::kActHardswish)
-    return MTR_E_PARAM;
-  if (mapping < -1 || mapping > 1) return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)w1 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)bias1 % 4) ||
-      ((uintptr_t)w_dw % 4) || ((uintptr_t)bias_dw % 4) || ((uintptr_t)row_mean % 4))
-    return MTR_E_ALIGN;
-  {  // y is written while other workgroups still read x
-    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y;
-    const uintptr_t xn = (uintptr_t)B * Cin * g.HW * 2, yn = (uintptr_t)B * Cmid * g.HW * 2;
-    if (x == y || (xb < yb + yn && yb < xb + xn)) return MTR_E_PARAM;
-  }
   if (B == 0) return MTR_OK;
   if (mapping >= 0) g.xcd_map = mapping;
-  const mtr::EdpArgs a = {x, w1, bias1, w_dw, bias_dw, y, row_mean, act1_code, act2_code, B, (hipStream_t)stream};
-  const int rc = dtype == MTR_F16 ? mtr::launch_expand_dw16_planes<MTR_F16>(a, g)
-                                  : mtr::launch_expand_dw16_planes<MTR_BF16>(a, g);
-  return rc;
+  return dtype == MTR_F16 ? mtr::launch_expand_dw16_planes<MTR_F16>(a, g)
+                          : mtr::launch_expand_dw16_planes<MTR_BF16>(a, g);
 }
 
 extern "C" int mtr_expand_dw16_planes(const void* x, int dtype, const void* w1, const float* bias1, int act1_code,

@@ -1,68 +1,37 @@
-// K27h: the 1x1 expand convolution of an MBConv block and the depthwise 3x3 convolution behind it (stride 1 or 2,
-// padding 1, f16 / bf16) in ONE launch on the LARGE planes K25h (expand_dw16.hip) and K26h (expand_dw16_planes.hip)
-// refuse -- 64x64, 128x128 -> 64x64, 32x32 -> 16x16 of MobileNetV3's early blocks -- where the expanded activation
-// written by K13h and read straight back by K11 is nearly all of the chain's traffic.  There is no squeeze-excite
-// mean: without it an output needs only its 3x3 window of the expanded activation, so a workgroup owns a BAND of
-// output rows instead of the whole plane and recomputes the halo rows of the expand.
+// K27h: the function of expand_dw16.h (stride 1 or 2, padding 1, no mean) on the LARGE planes K25h (expand_dw16.hip)
+// and K26h (expand_dw16_planes.hip) refuse -- 64x64, 128x128 -> 64x64, 32x32 -> 16x16 of MobileNetV3's early blocks --
+// where the expanded activation written by K13h and read straight back by K11 is nearly all of the chain's traffic.
+// There is no squeeze-excite mean: without it an output needs only its 3x3 window of the expanded activation, so a
+// workgroup owns a BAND of output rows instead of the whole plane and recomputes the halo rows of the expand.
 //
 // Not part of the reference's hot path (like K10 - K26h): backbones.fold_batchnorm(dtype=f16 / bf16,
-// fuse_expand_depthwise_tiles=True).  Per image b, stride s:
+// fuse_expand_depthwise_tiles=True).  The bits are those of conv1x1_16_kernel (K13h) followed by depthwise3x3_kernel
+// (K11's generic kernel, dw_finish).  A workgroup of four waves owns (image, chunk of 32 expanded channels, band of R
+// output rows):
 //
-//   mid[b, c, p] = rnd16(act1(bias1[c] + sum_k W1[c, k] * x[b, k, p]))                                    c < Cmid
-//   y[b, c, o]   = rnd16(act2(sum_{ky, kx} Wd[c, ky, kx] * mid[b, c, s * o + (ky - 1, kx - 1)] + bias2[c]))
-//
-// with the BITS of conv1x1_16_kernel (K13h) followed by depthwise3x3_kernel (K11's generic kernel, dw_finish).  A
-// workgroup of four waves owns (image, chunk of 32 expanded channels, band of R output rows):
-//
-//   phase 1  K13h's GEMM as K25h / K26h run it (16-k steps at k = 0, 16, ... on v_mfma_f32_32x32x16_{f16,bf16}, the
-//            same lane-to-k grouping and operand roles, k past Cin and positions past the band zero-filled; bias +
-//            activation in f32, one plain-cast rounding behind `settled`) over the s R + 3 - s input rows of the band,
-//            a contiguous span of positions of the plane (from the 16-byte boundary at or below its first row).
-//            K13h's bits do not depend on the tile.  The X^T image of a k-tile of 32 sits in ONE LDS buffer (the
-//            expands this kernel is for have one or two k-tiles); the next tile's global loads are in flight during
-//            the MFMAs.  Wave w runs the 32-position tiles w, w + 4, ...; all-zero 16-k steps are skipped (the
+//   phase 1  the pieces of expand_dw16.h over the s R + 3 - s input rows of the band, a contiguous span of positions of
+//            the plane (from the 16-byte boundary at or below its first row), in a loop of its own: the X^T image of
+//            a k-tile sits in ONE LDS buffer of a run-time row length (the expands this kernel is for have one or two
+//            k-tiles); the next tile's global loads are in flight during the MFMAs.  Wave w runs the 32-position
+//            tiles w, w + 4, ...; tiles past the band and all-zero 16-k steps are skipped (EdtBandTiles; the
 //            accumulator never holds -0, so they change no bit).
-//   between  the same LDS becomes the chunk's image [32][s R + 3 - s][LW] of the band (a channel's rows padded to 4
-//            elements mod 128, so that the 32 channels of an epilogue store fall into different banks): zeroed first
-//            -- the ring columns, and the ring row where the band touches the top (or, at stride 1, the bottom) of the
-//            plane -- then filled with the real rows, the neighbour bands' rows included.  Image column j sits at
-//            index j + 8.
+//   between  the chunk's image [32][s R + 3 - s][LW] of the band (a channel's rows padded to 4 elements mod 128, so
+//            that the 32 channels of an epilogue store fall into different banks): zeroed first -- the ring columns,
+//            and the ring row where the band touches the top (or, at stride 1, the bottom) of the plane -- then filled
+//            with the real rows, the neighbour bands' rows included.  Image column j sits at index j + 8.
 //   phase 2  per output dw_finish's arithmetic (accumulator from 0.0f, nine fmaf with ky outer and kx inner, acc +
 //            bias, activate, settled(), one rounding through K11's element types), no bounds test.  NOT the generic
 //            kernel's walk: 8, 16, ... 256 threads per channel (256 / live channels), a thread owns segments of 8 (OW %
 //            8 == 0) or 4 horizontally adjacent outputs, its window read from LDS, one 16- or 8-byte store each.
 //
 // The workgroups of one image run on one XCD, the chunks of a band next to each other, so x is re-read out of that
-// XCD's L2.  No atomics, no split-K, no workspace: the same inputs give the same bits.
-#include "common.h"
+// XCD's L2.
+#include "expand_dw16.h"
 
 namespace mtr {
 
-typedef float edt_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned short edt_u16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT> struct EdtBits;
-template <> struct EdtBits<MTR_F16> {
-  typedef __half T;  // K11's element type: phase 2 rounds and widens exactly as depthwise.hip does
-  typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-  static __device__ __forceinline__ edt_f32x16 mfma(uint4 a, uint4 b, edt_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
-  }
-};
-template <> struct EdtBits<MTR_BF16> {
-  typedef __hip_bfloat16 T;
-  typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ unsigned short rnd(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
-  static __device__ __forceinline__ edt_f32x16 mfma(uint4 a, uint4 b, edt_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
-  }
-};
-
-constexpr int kEdtBK = 32;       // k-tile of the X^T image
 constexpr int kEdtCM = 32;       // expanded channels per workgroup
 constexpr int kEdtColPad = 8;    // image column j of the chunk's image sits at index j + 8
-constexpr size_t kEdtMaxLds = 160 * 1024;
 constexpr size_t kEdtLdsTarget = 80 * 1024;  // what the band height is chosen for: two workgroups per CU
 
 struct EdtGeo {
@@ -77,17 +46,25 @@ struct EdtGeo {
   FastDiv d_w, d_ns, d_chunks, d_wgs;  // by W, ns, chunks, chunks * bands
 };
 
+// The 32-position tiles of wave `wave` over a band of n_pos staged positions, in k-tile t of Cin = K: tile j is the
+// band's tile 4 j + wave; tiles past the band do not run (wave-uniform), nor does a 16-k step past Cin (uniform: it
+// would add +0 to an accumulator that is never -0)
+struct EdtBandTiles {
+  int wave, n_pos, t, K;
+  __device__ __forceinline__ int pos(int j) const { return 32 * (4 * j + wave); }
+  __device__ __forceinline__ bool step(int s) const { return t * kEdwBK + 16 * s < K; }
+  __device__ __forceinline__ bool tile(int j) const { return pos(j) < n_pos; }
+};
+
 // FN 32-position tiles per wave, four waves along the positions: BN = 128 FN staged positions per band
 template <int DT, int S, int FN>
 __global__ __launch_bounds__(256) void expand_dw16_tiles_kernel(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ w1, const float* __restrict__ bias1,
     const float* __restrict__ wd, const float* __restrict__ bias2, unsigned short* __restrict__ y, EdtGeo g, int B,
     int act1, int act2) {
-  using Hh = EdtBits<DT>;
+  using Hh = EdwBits<DT>;
   using T = typename Hh::T;
-  constexpr int CM = kEdtCM, BN = 128 * FN, BK = kEdtBK, KS = BK / 16;
-  constexpr int UNITS = (BK / 4) * (BN / 8);  // loader units of 4 k x 8 positions
-  constexpr int NU = UNITS / 256;             // units per loader thread
+  constexpr int CM = kEdtCM, BN = 128 * FN, BK = kEdwBK, KS = kEdwKS;
   extern __shared__ __attribute__((aligned(16))) unsigned short edt_lds[];
   unsigned short* xs = edt_lds;  // phase 1: [BN][ldk], the X^T image of a k-tile
   unsigned short* ms = edt_lds;  // afterwards: [CM][rows_img][LW], the chunk's band of the expanded activation
@@ -114,121 +91,41 @@ __global__ __launch_bounds__(256) void expand_dw16_tiles_kernel(
   const int n_pos32 = (n_pos + 31) & ~31;
   const int ldk = g.ldk;
 
-  // ---- phase 1: conv1x1_16_kernel's loop over the positions p_base .. p_hi - 1 of one image
+  // ---- phase 1: conv1x1_16_kernel's loop over the positions p_base .. p_hi - 1 of one image; this lane's channel:
+  // r of the chunk
   const unsigned short* xb = x + (long long)b * K * HW + p_base;
-  edt_u16x8 xr[NU][4];
-  auto load_x = [&](int k0) {
-#pragma unroll
-    for (int n = 0; n < NU; ++n) {
-      const int u = tid + 256 * n;
-      const int p8 = u % (BN / 8), k4 = u / (BN / 8);
-      const bool on = 8 * p8 < n_pos;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int k = k0 + 4 * k4 + i;
-        edt_u16x8 t = (edt_u16x8)0;
-        if (on && k < K)
-          t = __builtin_bit_cast(edt_u16x8, *reinterpret_cast<const uint4*>(xb + (long long)k * HW + 8 * p8));
-        xr[n][i] = t;
-      }
-    }
-  };
-  auto store_x = [&]() {  // 4 k-rows x 8 positions -> 8 positions x 4 k of the X^T image
-#pragma unroll
-    for (int n = 0; n < NU; ++n) {
-      const int u = tid + 256 * n;
-      const int p8 = u % (BN / 8), k4 = u / (BN / 8);
-      if (8 * p8 < n_pos32 && 4 * k4 + 8 < ldk) {  // (the tiles that run; the k columns the image has)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          uint2 v;
-          v.x = (unsigned)xr[n][0][j] | ((unsigned)xr[n][1][j] << 16);
-          v.y = (unsigned)xr[n][2][j] | ((unsigned)xr[n][3][j] << 16);
-          *reinterpret_cast<uint2*>(&xs[(8 * p8 + j) * ldk + 4 * k4]) = v;
-        }
-      }
-    }
-  };
-  // this lane's weight fragments: row m0 + r, k 16 s + 8 h .. + 7 of each k-tile
-  const int mrow = m0 + r;
-  auto load_w = [&](uint4 (&wr)[KS], int k0) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int k = k0 + 16 * s + 8 * h;
-      uint4 t = make_uint4(0u, 0u, 0u, 0u);
-      if (mrow < M && k < K) t = *reinterpret_cast<const uint4*>(w1 + (long long)mrow * K + k);
-      wr[s] = t;
-    }
-  };
-
-  edt_f32x16 acc[FN];
-#pragma unroll
-  for (int j = 0; j < FN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[j][e] = 0.0f;
-
-  uint4 wc[KS], wnx[KS];
+  EdtBandTiles tiles = {wave, n_pos, 0, K};
+  EdwXTile<BN> xt;
+  edw_f32x16 acc[1][FN];
+  edw_clear(acc);
+  uint4 wc[1][KS], wnx[1][KS];
   const int n_tiles = (K + BK - 1) / BK;
-  load_x(0);
-  load_w(wc, 0);
+  xt.load(xb, tid, 0, K, HW, n_pos);
+  edw_load_w(wc, w1, m0 + r, M, K, 0, h);
   for (int t = 0; t < n_tiles; ++t) {
-    store_x();
+    // (the tiles that run; the k columns the image has)
+    xt.store(xs, ldk, tid, [&](int p8, int k4) { return 8 * p8 < n_pos32 && 4 * k4 + 8 < ldk; });
     __syncthreads();
     if (t + 1 < n_tiles) {  // in flight during this tile's MFMAs
-      load_x((t + 1) * BK);
-      load_w(wnx, (t + 1) * BK);
+      xt.load(xb, tid, (t + 1) * BK, K, HW, n_pos);
+      edw_load_w(wnx, w1, m0 + r, M, K, (t + 1) * BK, h);
     }
-    const unsigned short* xa = &xs[r * ldk + 8 * h];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if (t * BK + 16 * s < K) {  // (uniform) a 16-k step past Cin adds +0 to an accumulator that is never -0
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          const int p0 = 32 * (4 * j + wave);
-          if (p0 < n_pos) {  // (wave-uniform) tiles past the band do not run
-            const uint4 a = *reinterpret_cast<const uint4*>(xa + p0 * ldk + 16 * s);
-            acc[j] = Hh::mfma(a, wc[s], acc[j]);
-          }
-        }
-      }
-    }
+    tiles.t = t;
+    edw_mfma_ktile<Hh>(acc, wc, &xs[r * ldk + 8 * h], ldk, tiles);
     __syncthreads();  // the image is read: the next tile's, or the chunk's image, may overwrite it
     if (t + 1 < n_tiles) {
 #pragma unroll
-      for (int s = 0; s < KS; ++s) wc[s] = wnx[s];
+      for (int s = 0; s < KS; ++s) wc[0][s] = wnx[0][s];
     }
   }
 
-  // ---- zero the chunk's image, ring included
-  {
-    const int n16 = (CM * g.plane) >> 3;  // (LW % 4 == 0, CM % 2 == 0: whole 16-byte groups)
-    for (int i = tid; i < n16; i += 256) reinterpret_cast<uint4*>(ms)[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  // ---- the chunk's image, ring included (LW % 4 == 0, CM % 2 == 0: whole 16-byte groups)
+  edw_zero_image(ms, CM * g.plane, tid);
   __syncthreads();
-  // K13h's epilogue: the lane holds channel m0 + r, positions 8 q + 4 h + 0 .. 3 of each 32-position tile (inside one
-  // row of the plane: W % 4 == 0, p_base % 4 == 0)
-  auto epilogue = [&](auto tag) {
-    constexpr int ACT = decltype(tag)::value;
-    if (m0 + r >= M) return;
-    const float bm = bias1[m0 + r];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const int p = p_base + 32 * (4 * j + wave) + 8 * qq + 4 * h;
-        if (p < p_lo || p >= p_hi) continue;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = settled(activate<ACT>(acc[j][4 * qq + e] + bm));
-        uint2 o;
-        o.x = (unsigned)Hh::rnd(v[0]) | ((unsigned)Hh::rnd(v[1]) << 16);
-        o.y = (unsigned)Hh::rnd(v[2]) | ((unsigned)Hh::rnd(v[3]) << 16);
-        const int row = (int)fastdiv((unsigned)p, g.d_w), col = p - row * g.W;
-        *reinterpret_cast<uint2*>(&ms[r * g.plane + (row - iy0) * g.LW + kEdtColPad + col]) = o;
-      }
-    }
-  };
-  with_act(act1, epilogue);
+  edw_store_expanded<Hh>(
+      acc, act1, bias1, m0, M, r, h, tiles, p_base, p_lo, p_hi,
+      [&](int p, int& row, int& col) { row = (int)fastdiv((unsigned)p, g.d_w), col = p - row * g.W; },
+      EdwImage{ms, g.plane, g.LW, iy0, kEdtColPad});
   __syncthreads();
 
   // ---- phase 2: dw_finish's arithmetic per output, the taps from LDS (the ring is zero: no masks)
@@ -290,19 +187,6 @@ __global__ __launch_bounds__(256) void expand_dw16_tiles_kernel(
   });
 }
 
-static int edt_ilog2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
-// launch_depthwise's condition for K11's stride-1 block kernel (depthwise.hip), restated for a 16-byte aligned x
-static bool edt_k11_block_plane(int H, int W) {
-  if (H % 4 || W % 4) return false;
-  const int tw = edt_ilog2_exact(W / 4), th = edt_ilog2_exact(H / 4);
-  return tw >= 0 && tw <= 4 && th >= 0 && tw + th <= 6;
-}
-
 // elements per channel of the image of `rows` rows: 4 (mod 128), two LDS banks from one channel to the next -- phase
 // 1's epilogue writes one 8-byte group per channel (lane) at the same row and column
 static int edt_plane(const EdtGeo& g, int rows) { return (rows * g.LW + 123) / 128 * 128 + 4; }
@@ -322,7 +206,7 @@ static int expand_dw16_tiles_shape(EdtGeo& g, long long B, int Cin, int Cmid, in
   if (H > 128 || W > 128) return MTR_E_SHAPE;
   if (stride == 1) {
     if (W % 4 || W < 4 || (H * W) % 8) return MTR_E_SHAPE;  // whole groups of four outputs, of eight positions
-    if (edt_k11_block_plane(H, W)) return MTR_E_SHAPE;      // (K11's block kernel: other bits)
+    if (edw_k11_block_plane(H, W)) return MTR_E_SHAPE;      // (K11's block kernel: other bits)
   } else {
     if (H % 2 || W % 8) return MTR_E_SHAPE;  // padding 1 on all four sides, OW % 4 == 0
   }
@@ -333,7 +217,7 @@ static int expand_dw16_tiles_shape(EdtGeo& g, long long B, int Cin, int Cmid, in
   g.OH = stride == 1 ? H : H / 2, g.OW = stride == 1 ? W : W / 2;
   // column j at index j + 8; stride 1 reads one column right of the plane, rows stay whole 16-byte groups
   g.LW = stride == 1 ? (W + kEdtColPad + 1 + 7) / 8 * 8 : W + kEdtColPad;
-  g.ldk = (Cin <= 16 ? 16 : kEdtBK) + 8;
+  g.ldk = (Cin <= 16 ? 16 : kEdwBK) + 8;
   g.chunks = (Cmid + kEdtCM - 1) / kEdtCM;
   g.sw8 = g.OW % 8 == 0;
   g.ns = g.OW / (g.sw8 ? 8 : 4);
@@ -343,49 +227,29 @@ static int expand_dw16_tiles_shape(EdtGeo& g, long long B, int Cin, int Cmid, in
   return MTR_OK;
 }
 
-struct EdtArgs {
-  const void *x, *w1;
-  const float *bias1, *wd, *bias2;
-  void* y;
-  int act1, act2;
-  long long B;
-  hipStream_t stream;
-};
-
-// y == NULL: the shape query (mtr_expand_dw16_tiles_lds_bytes), -> the bytes of LDS, no launch
 template <int DT, int S, int FN>
-static int launch_expand_dw16_tiles_cfg(const EdtArgs& a, EdtGeo g, int R) {
+static int launch_expand_dw16_tiles_cfg(const EdwArgs& a, EdtGeo g, int R) {
   constexpr int BN = 128 * FN;
   g.R = R;
   g.rows_img = S * R + 3 - S;
   g.plane = edt_plane(g, g.rows_img);
   g.bands = (g.OH + R - 1) / R;
   g.d_wgs = make_fastdiv((unsigned)(g.chunks * g.bands));
-  const size_t xs_bytes = (size_t)BN * g.ldk * sizeof(unsigned short);
-  const size_t ms_bytes = (size_t)kEdtCM * g.plane * sizeof(unsigned short);
-  const size_t lds = xs_bytes > ms_bytes ? xs_bytes : ms_bytes;
-  if (lds > kEdtMaxLds) return MTR_E_SHAPE;
-  const long long gx = (a.B + 7) / 8 * 8 * g.chunks * g.bands;
-  if (gx > 0x7fffffffLL) return MTR_E_SHAPE;
-  if (!a.y) return (int)lds;
   auto kern = expand_dw16_tiles_kernel<DT, S, FN>;
-  if (lds > 64 * 1024) {
-    const int e = allow_dynamic_lds((const void*)kern, kEdtMaxLds);
-    if (e != MTR_OK) return e;
-  }
-  MTR_CLEAR_STALE();
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, a.stream, (const unsigned short*)a.x,
-                     (const unsigned short*)a.w1, a.bias1, a.wd, a.bias2, (unsigned short*)a.y, g, (int)a.B, a.act1,
-                     a.act2);
-  MTR_CHECK_LAUNCH();
-  return MTR_OK;
+  return edw_launch((const void*)kern, a, (size_t)BN * g.ldk * sizeof(unsigned short),
+                    (size_t)kEdtCM * g.plane * sizeof(unsigned short), (a.B + 7) / 8 * 8 * g.chunks * g.bands,
+                    [&](dim3 grid, size_t lds) {
+                      hipLaunchKernelGGL(kern, grid, dim3(256), lds, a.stream, (const unsigned short*)a.x,
+                                         (const unsigned short*)a.w1, a.bias1, a.wd, a.bias2, (unsigned short*)a.y, g,
+                                         (int)a.B, a.act1, a.act2);
+                    });
 }
 
 // the only place that maps a shape to the band height and the template parameters: the tallest band up to 8
 // (stride 1) or 4 (stride 2) output rows whose input rows fit 512 staged positions; 1024 where that leaves fewer than
 // 6 (3) rows -- rows of more than 64 (stride 2: 72) positions
 template <int DT, int S>
-static int launch_expand_dw16_tiles(const EdtArgs& a, const EdtGeo& g) {
+static int launch_expand_dw16_tiles(const EdwArgs& a, const EdtGeo& g) {
   const int cap = S == 1 ? 8 : 4, want = S == 1 ? 6 : 3;
   auto tallest = [&](int BN) {
     int R = g.OH < cap ? g.OH : cap;
@@ -400,7 +264,7 @@ static int launch_expand_dw16_tiles(const EdtArgs& a, const EdtGeo& g) {
 }
 
 template <int DT>
-static int launch_expand_dw16_tiles_stride(const EdtArgs& a, const EdtGeo& g, int stride) {
+static int launch_expand_dw16_tiles_stride(const EdwArgs& a, const EdtGeo& g, int stride) {
   return stride == 1 ? launch_expand_dw16_tiles<DT, 1>(a, g) : launch_expand_dw16_tiles<DT, 2>(a, g);
 }
 
@@ -410,7 +274,7 @@ extern "C" size_t mtr_expand_dw16_tiles_lds_bytes(long long B, int Cin, int Cmid
   mtr::EdtGeo g;
   if (B <= 0 || mtr::expand_dw16_tiles_shape(g, B, Cin, Cmid, H, W, stride) != MTR_OK) return 0;
   // (the tile and LDS rules do not depend on the dtype)
-  mtr::EdtArgs a = {};
+  mtr::EdwArgs a = {};
   a.B = B;
   const int n = mtr::launch_expand_dw16_tiles_stride<MTR_F16>(a, g, stride);
   return n > 0 ? (size_t)n : 0;
@@ -419,24 +283,15 @@ extern "C" size_t mtr_expand_dw16_tiles_lds_bytes(long long B, int Cin, int Cmid
 extern "C" int mtr_expand_dw16_tiles(const void* x, int dtype, const void* w1, const float* bias1, int act1_code,
                                      const float* w_dw, const float* bias_dw, int act2_code, long long B, int Cin,
                                      int Cmid, int H, int W, int stride, void* y, mtr_stream_t stream) {
-  if (!x || !w1 || !bias1 || !w_dw || !bias_dw || !y) return MTR_E_NULL;
-  if (dtype != MTR_F16 && dtype != MTR_BF16) return MTR_E_DTYPE;
+  const mtr::EdwArgs a = {x, w1, bias1, w_dw, bias_dw, y, nullptr, act1_code, act2_code, B, (hipStream_t)stream};
   mtr::EdtGeo g;
-  const int e = mtr::expand_dw16_tiles_shape(g, B, Cin, Cmid, H, W, stride);
+  const int e = mtr::edw_check(a, dtype, Cin, Cmid, -1, [&](int& hw_in, int& hw_out) {
+    const int es = mtr::expand_dw16_tiles_shape(g, B, Cin, Cmid, H, W, stride);
+    if (es == MTR_OK) hw_in = g.HW, hw_out = g.OH * g.OW;
+    return es;
+  });
   if (e != MTR_OK) return e;
-  if (act1_code < mtr::kActNone || act1_code > mtr::kActHardswish || act2_code < mtr::kActNone ||
-      act2_code > mtr::kActHardswish)
-    return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)w1 % 16) || ((uintptr_t)y % 16) || ((uintptr_t)bias1 % 4) ||
-      ((uintptr_t)w_dw % 4) || ((uintptr_t)bias_dw % 4))
-    return MTR_E_ALIGN;
-  {  // y is written while other workgroups still read x
-    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y;
-    const uintptr_t xn = (uintptr_t)B * Cin * g.HW * 2, yn = (uintptr_t)B * Cmid * g.OH * g.OW * 2;
-    if (x == y || (xb < yb + yn && yb < xb + xn)) return MTR_E_PARAM;
-  }
   if (B == 0) return MTR_OK;
-  const mtr::EdtArgs a = {x, w1, bias1, w_dw, bias_dw, y, act1_code, act2_code, B, (hipStream_t)stream};
   return dtype == MTR_F16 ? mtr::launch_expand_dw16_tiles_stride<MTR_F16>(a, g, stride)
                           : mtr::launch_expand_dw16_tiles_stride<MTR_BF16>(a, g, stride);
 }

@@ -991,19 +991,47 @@ def fused_mbconv16(x, w3_packed, bias3, act, stride, w1, bias1, residual=None, o
 EXPAND_DW16_MAPPINGS = {'auto': -1, 'plain': 0, 'xcd': 1}
 
 
-def expand_depthwise16_supported(x, w1):
-    """Whether mtr_expand_dw16 takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous, both
-    16-byte aligned, Cin a multiple of 8, an [.., H, W] plane K11 runs on its stride-1 block kernel
-    (k11_takes_block_kernel) of at most 256 positions, fewer than 2^24 planes of output (its MTR_E_DTYPE /
-    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w1` is the expand's weight, [Cmid, Cin] or
-    [Cmid, Cin, 1, 1]."""
+def _expand_dw16_supported(x, w1, query, *extra):
+    """The tensor rules K25h, K26h and K27h share, then the C library's own shape query `query`(B, Cin, Cmid, H, W,
+    *extra) > 0."""
     if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
             or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
         return False
     B, K, H, W = x.shape
     if w1.numel() != w1.shape[0] * K:
         return False
-    return _lib.load().mtr_expand_dw16_lds_bytes(B, K, w1.shape[0], H, W) > 0
+    return getattr(_lib.load(), query)(B, K, w1.shape[0], H, W, *extra) > 0
+
+
+def _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, stride=1):
+    """The argument checks of the wrapper `name`, in their order -> (B, Cin, Cmid, H, W, w1 as [Cmid, Cin]).  `stride`
+    is expand_depthwise16_tiles' alone (the other two have none and leave the default): its refusal keeps its place,
+    right behind x's."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f'{name}: x must be [B, Cin, H, W], NCHW-contiguous')
+    if stride not in (1, 2):
+        raise ValueError(f'{name}: stride must be 1 or 2, got {stride}')
+    B, K, H, W = x.shape
+    Cmid = w1.shape[0]
+    w1 = w1.reshape(Cmid, -1)
+    if w1.shape[1] != K:
+        raise ValueError(f'{name}: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
+    if w1.dtype != x.dtype:
+        raise ValueError(f'{name}: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
+    if w_dw.numel() != Cmid * 9:
+        raise ValueError(f'{name}: the depthwise weight must be [{Cmid}, 3, 3], got {tuple(w_dw.shape)}')
+    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
+        raise ValueError(f'{name}: biases have {bias1.numel()} and {bias_dw.numel()} elements, expected {Cmid} each')
+    return B, K, Cmid, H, W, w1
+
+
+def expand_depthwise16_supported(x, w1):
+    """Whether mtr_expand_dw16 takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous, both
+    16-byte aligned, Cin a multiple of 8, an [.., H, W] plane K11 runs on its stride-1 block kernel
+    (k11_takes_block_kernel) of at most 256 positions, fewer than 2^24 planes of output (its MTR_E_DTYPE /
+    MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w1` is the expand's weight, [Cmid, Cin] or
+    [Cmid, Cin, 1, 1]."""
+    return _expand_dw16_supported(x, w1, 'mtr_expand_dw16_lds_bytes')
 
 
 def expand_depthwise16(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False, out=None, mapping='auto'):
@@ -1017,20 +1045,7 @@ def expand_depthwise16(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False,
     (expand_depthwise16_supported asks first); there is no fallback in here."""
     require_cuda(x, w1, bias1, w_dw, bias_dw, out)
     code = EXPAND_DW16_MAPPINGS[mapping]
-    if x.dim() != 4 or not x.is_contiguous():
-        raise ValueError('expand_depthwise16: x must be [B, Cin, H, W], NCHW-contiguous')
-    B, K, H, W = x.shape
-    Cmid = w1.shape[0]
-    w1 = w1.reshape(Cmid, -1)
-    if w1.shape[1] != K:
-        raise ValueError(f'expand_depthwise16: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
-    if w1.dtype != x.dtype:
-        raise ValueError(f'expand_depthwise16: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
-    if w_dw.numel() != Cmid * 9:
-        raise ValueError(f'expand_depthwise16: the depthwise weight must be [{Cmid}, 3, 3], got {tuple(w_dw.shape)}')
-    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
-        raise ValueError(f'expand_depthwise16: biases have {bias1.numel()} and {bias_dw.numel()} elements, expected '
-                         f'{Cmid} each')
+    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16', x, w1, bias1, w_dw, bias_dw)
     out = _residual_and_out('expand_depthwise16', x, (B, Cmid, H, W), None, out)
     mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
     args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
@@ -1052,13 +1067,7 @@ def expand_depthwise16_planes_supported(x, w1):
     and H W at most 576 that K11 does NOT run on its stride-1 block kernel (k11_takes_block_kernel), fewer than 2^30
     planes of output (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).  `w1` is the
     expand's weight, [Cmid, Cin] or [Cmid, Cin, 1, 1]."""
-    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
-            or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
-        return False
-    B, K, H, W = x.shape
-    if w1.numel() != w1.shape[0] * K:
-        return False
-    return _lib.load().mtr_expand_dw16_planes_lds_bytes(B, K, w1.shape[0], H, W) > 0
+    return _expand_dw16_supported(x, w1, 'mtr_expand_dw16_planes_lds_bytes')
 
 
 def expand_depthwise16_planes(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False, out=None, mapping='auto'):
@@ -1070,21 +1079,7 @@ def expand_depthwise16_planes(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean
     there is no fallback in here."""
     require_cuda(x, w1, bias1, w_dw, bias_dw, out)
     code = EXPAND_DW16_MAPPINGS[mapping]
-    if x.dim() != 4 or not x.is_contiguous():
-        raise ValueError('expand_depthwise16_planes: x must be [B, Cin, H, W], NCHW-contiguous')
-    B, K, H, W = x.shape
-    Cmid = w1.shape[0]
-    w1 = w1.reshape(Cmid, -1)
-    if w1.shape[1] != K:
-        raise ValueError(f'expand_depthwise16_planes: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
-    if w1.dtype != x.dtype:
-        raise ValueError(f'expand_depthwise16_planes: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
-    if w_dw.numel() != Cmid * 9:
-        raise ValueError(f'expand_depthwise16_planes: the depthwise weight must be [{Cmid}, 3, 3], got '
-                         f'{tuple(w_dw.shape)}')
-    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
-        raise ValueError(f'expand_depthwise16_planes: biases have {bias1.numel()} and {bias_dw.numel()} elements, '
-                         f'expected {Cmid} each')
+    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_planes', x, w1, bias1, w_dw, bias_dw)
     out = _residual_and_out('expand_depthwise16_planes', x, (B, Cmid, H, W), None, out)
     mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
     args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
@@ -1106,13 +1101,7 @@ def expand_depthwise16_tiles_supported(x, w1, stride=1):
     W % 4 == 0, H W % 8 == 0 and a plane K11 does NOT run on its stride-1 block kernel (k11_takes_block_kernel); at
     stride 2 H even and W % 8 == 0 (its MTR_E_DTYPE / MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch).
     `w1` is the expand's weight, [Cmid, Cin] or [Cmid, Cin, 1, 1]."""
-    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16) or w1.dtype != x.dtype \
-            or not x.is_contiguous() or not w1.is_contiguous() or x.data_ptr() % 16 or w1.data_ptr() % 16:
-        return False
-    B, K, H, W = x.shape
-    if w1.numel() != w1.shape[0] * K:
-        return False
-    return _lib.load().mtr_expand_dw16_tiles_lds_bytes(B, K, w1.shape[0], H, W, int(stride)) > 0
+    return _expand_dw16_supported(x, w1, 'mtr_expand_dw16_tiles_lds_bytes', int(stride))
 
 
 def expand_depthwise16_tiles(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, out=None):
@@ -1123,23 +1112,7 @@ def expand_depthwise16_tiles(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, 
     same on every call and graph replay.  What the kernel does not take raises (expand_depthwise16_tiles_supported
     asks first); there is no fallback in here."""
     require_cuda(x, w1, bias1, w_dw, bias_dw, out)
-    if x.dim() != 4 or not x.is_contiguous():
-        raise ValueError('expand_depthwise16_tiles: x must be [B, Cin, H, W], NCHW-contiguous')
-    if stride not in (1, 2):
-        raise ValueError(f'expand_depthwise16_tiles: stride must be 1 or 2, got {stride}')
-    B, K, H, W = x.shape
-    Cmid = w1.shape[0]
-    w1 = w1.reshape(Cmid, -1)
-    if w1.shape[1] != K:
-        raise ValueError(f'expand_depthwise16_tiles: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
-    if w1.dtype != x.dtype:
-        raise ValueError(f'expand_depthwise16_tiles: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
-    if w_dw.numel() != Cmid * 9:
-        raise ValueError(f'expand_depthwise16_tiles: the depthwise weight must be [{Cmid}, 3, 3], got '
-                         f'{tuple(w_dw.shape)}')
-    if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
-        raise ValueError(f'expand_depthwise16_tiles: biases have {bias1.numel()} and {bias_dw.numel()} elements, '
-                         f'expected {Cmid} each')
+    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_tiles', x, w1, bias1, w_dw, bias_dw, stride)
     out = _residual_and_out('expand_depthwise16_tiles', x, (B, Cmid, H // stride, W // stride), None, out)
     check(_lib.load().mtr_expand_dw16_tiles(
         _ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],

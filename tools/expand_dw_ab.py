@@ -38,18 +38,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HBM_TBS = 6.29
-# per kernel: the fold_batchnorm option, the expand's field, the class switch and list of DepthwiseBiasAct, its question,
-# the wrapper and the LDS query, and the (backbone, batch, px) measured
+# per kernel, beside what backbones.EXPAND_DW_KERNELS says of it (option, field, switch, slower, takes, fn, strided): the
+# LDS query and the (backbone, batch, px) measured
 KERNELS = {
-    'k25h': dict(option='fuse_expand_depthwise', field='hand_to', switch='use_k25h', slower='k25h_slower',
-                 takes='k25h_takes', fn='expand_depthwise16', lds='mtr_expand_dw16_lds_bytes',
-                 workloads=[('effnetv2-s', 64, 256), ('mobilenetv3', 320, 256)]),
-    'k26h': dict(option='fuse_expand_depthwise_planes', field='hand_planes_to', switch='use_k26h',
-                 slower='k26h_slower', takes='k26h_takes', fn='expand_depthwise16_planes',
-                 lds='mtr_expand_dw16_planes_lds_bytes', workloads=[('effnetv2-l', 32, 384), ('effnetv2-s', 64, 384)]),
-    'k27h': dict(option='fuse_expand_depthwise_tiles', field='hand_tiles_to', switch='use_k27h',
-                 slower='k27h_slower', takes='k27h_takes', fn='expand_depthwise16_tiles',
-                 lds='mtr_expand_dw16_tiles_lds_bytes', workloads=[('mobilenetv3', 320, 256)], strided=True),
+    'k25h': dict(lds='mtr_expand_dw16_lds_bytes', workloads=[('effnetv2-s', 64, 256), ('mobilenetv3', 320, 256)]),
+    'k26h': dict(lds='mtr_expand_dw16_planes_lds_bytes', workloads=[('effnetv2-l', 32, 384), ('effnetv2-s', 64, 384)]),
+    'k27h': dict(lds='mtr_expand_dw16_tiles_lds_bytes', workloads=[('mobilenetv3', 320, 256)]),
 }
 
 
@@ -66,7 +60,7 @@ def armed_pairs(net, res, cfg):
                 x = args[0]
                 dw = getattr(mod, cfg['field'])[0]
                 key = (mod.conv.in_channels, mod.conv.out_channels, x.shape[2], x.shape[3])
-                out.setdefault(key + ((dw.stride,) if cfg.get('strided') else ()), []).append((mod, dw))
+                out.setdefault(key + ((dw.stride,) if cfg['strided'] else ()), []).append((mod, dw))
             hooks.append(m.register_forward_pre_hook(hook))
     setattr(backbones.DepthwiseBiasAct, cfg['switch'], False)
     try:
@@ -87,10 +81,11 @@ def main():
     ap.add_argument('--kernel', choices=sorted(KERNELS), default='k25h')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    kn, cfg = args.kernel, KERNELS[args.kernel]
+    kn = args.kernel
     sys.path.insert(0, ROOT)
     import torch
     from metrabs_amd import backbones, kernels
+    cfg = dict(backbones.EXPAND_DW_KERNELS[kn], **KERNELS[kn])
     DW = backbones.DepthwiseBiasAct
     listed = getattr(DW, cfg['slower'])
     setattr(DW, cfg['slower'], frozenset())   # measure every shape, listed or not
@@ -199,7 +194,7 @@ def main():
                                share_of_byte_floor=round(floor / tk, 3), equal_bits=equal,
                                slower=not ahead_every_round,
                                lds_bytes=int(getattr(kernels._lib.load(), cfg['lds'])(
-                                   B, Cin, Cmid, H, W, *((stride,) if cfg.get('strided') else ()))))
+                                   B, Cin, Cmid, H, W, *((stride,) if cfg['strided'] else ()))))
                     if not ahead_every_round:
                         losers.add(key)
                 rows.append(row)
