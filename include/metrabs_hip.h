@@ -760,6 +760,38 @@ int mtr_conv3x3s2_bias_act(const void* x, const float* w_packed /*[Cin/4][Cout][
  * weight), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_conv3x3s2_lds_bytes(long long B, int Cin, int Cout, int H, int W);
 
+/* K21 (outside the reference's hot path, like K10): a dense 3x3 convolution of f32 tensors -- stride 1, padding 1 on
+ * all sides, no dilation, groups 1 -- on the bf16 matrix cores by operand split (K20's arithmetic), with the K10
+ * epilogue folded in:
+ *   y[b, m, oy, ox] = act(bias[m] + sum_{ci, ky, kx} w[m, ci, ky, kx] * x[b, ci, oy + ky - 1, ox + kx - 1])
+ *                     (+ residual[b, m, oy, ox])
+ * x [B, Cin, H, W], y and residual [B, Cout, H, W]: f32, NCHW, contiguous, 16-byte aligned (else MTR_E_ALIGN).
+ * w_split is the f32 OIHW weight as three bf16 pieces, [3][Cout][3][3][Cp], ci innermost, Cp = Cin rounded up to 16
+ * with a zero tail (kernels.pack_conv3x3_split_weight): piece 0 = bf16(w), piece 1 = bf16(w - p0), piece 2 =
+ * bf16(w - p0 - p1), their sum is w exactly; contiguous, 16-byte aligned.  bias [Cout] f32; residual may be NULL and
+ * may be x itself (Cin == Cout); act_code as the `act` of mtr_bias_act_nchw, applied in K10's order (bias,
+ * activation, then the residual), else MTR_E_PARAM (also with B == 0).
+ * x is split the same way on the fly.  Every output element is ONE f32 accumulator that starts from 0 and takes, for
+ * c = 0, 16, .. < Cp (chunks of 16 input channels, the same constant for every shape), for ky, for kx, the six piece
+ * products (w2,v0), (w0,v2), (w1,v1), (w1,v0), (w0,v1), (w0,v0) in this order, each one v_mfma_f32_32x32x16_bf16 over
+ * the chunk's 16 channels; padding taps enter as zeros; the three products below 2^-23 |w v| are dropped.
+ * a - bf16(a) of an infinity is NaN: a window that holds an infinity (or |x| >= 2^127 (2 - 2^-8)) gives NaN.
+ * MTR_E_SHAPE (the caller keeps another path) unless Cin % 8 == 0, W % 4 == 0, H >= 1, Cout >= 1, B >= 0, and
+ * B Cin H W, B Cout H W, 27 Cout Cp and the grid are below 2^31; no shape inside this domain is refused for LDS.  A
+ * NULL x, w_split, bias or y is MTR_E_NULL; y overlapping x or residual is MTR_E_PARAM.  The checks are made on the
+ * host, in the order NULL, shape, act_code, alignment, overlap, before anything is enqueued; B == 0 returns MTR_OK
+ * without a launch.  No atomics, no split-K, no workspace, nothing allocated; only enqueues on `stream`: the same
+ * inputs give the same bits for any batch index, tile position and residual, on every call and graph replay.  (The
+ * activation parameter is named act_code, as K22's; this entry's refusals are pinned in
+ * tests/test_conv3x3_split_host.py.) */
+int mtr_conv3x3_bias_act_split(const void* x, const void* w_split /*[3][Cout][3][3][Cp] bf16*/, const float* bias,
+                               const void* residual, int act_code, long long B, int Cin, int Cout, int H, int W,
+                               void* y, mtr_stream_t stream);
+
+/* The bytes of LDS one workgroup of mtr_conv3x3_bias_act_split uses (two buffers of one 16-channel chunk of the split
+ * input halo), or 0 where the entry answers MTR_E_SHAPE (and for B <= 0).  No GPU work. */
+size_t mtr_conv3x3_split_lds_bytes(long long B, int Cin, int Cout, int H, int W);
+
 /* K25h (outside the reference's hot path, like K10): the 1x1 expand convolution of an MBConv block and the depthwise
  * 3x3 stride-1 padding-1 convolution behind it, of f16 / bf16 tensors, as ONE launch; the Cmid-wide activation between
  * them stays in LDS (no workspace, nothing allocated, graph-capturable):

@@ -188,6 +188,9 @@ SIGNATURES = {
     'mtr_conv3x3s2_bias_act': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                        c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_conv3x3s2_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int]),
+    'mtr_conv3x3_bias_act_split': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                           c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mtr_conv3x3_split_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int]),
     'mtr_expand_dw16': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                 ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'mtr_expand_dw16_opts': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,

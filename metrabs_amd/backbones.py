@@ -161,7 +161,7 @@ class FusedMBConv(nn.Module):
     # set by fold_batchnorm(fuse_blocks=True) on a 16-bit copy: (the block's Conv3x3BiasAct, its project
     # ConvBiasAct) -- references, as SqueezeExcite.mean_from: nothing is registered twice, no weight is copied
     fused_pair = ()
-    # 'k16h' / 'k13_pre' / 'k20_pre' / 'k19' / 'k22' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
+    # 'k16h' / 'k13_pre' / 'k20_pre' / 'k19' / 'k21' / 'k22' or 'chain': what the last forward of an armed block ran (tests, A/B runs); None on
     # every other block
     last_path = None
     # class-wide switch (tests and A/B runs): the two-kernel chain everywhere
@@ -204,7 +204,7 @@ class FusedMBConv(nn.Module):
         epilogue on K19, then the project and the skip as an ordinary call of the project layer -- K13, or K20 under
         split_gemm (the project's own last_path says which).  With K19 switched off or refusing, a
         WinogradConv3x3BiasAct in pre_pair[0] is the ConvBiasAct it derives from, and the block takes the other
-        branches.  'k22' (fold_batchnorm(strided3x3=True)): the same for a stride-2 first layer, a
+        branches.  'k21' (fold_batchnorm(split3x3=True)): as 'k19', a SplitConv3x3BiasAct on K21.  'k22' (fold_batchnorm(strided3x3=True)): the same for a stride-2 first layer, a
         StridedConv3x3BiasAct, on K22.  'chain': what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
         nothing for them; the tensor without its epilogue goes to the project alone, which applies that epilogue on
         every path, and no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the
@@ -212,12 +212,18 @@ class FusedMBConv(nn.Module):
         first, project = self.pre_pair
         c = first.conv
         residual = x if self.residual else None
-        if isinstance(first, WinogradConv3x3BiasAct) and first.path(x) == 'k19':
+        first_path = first.path(x) if isinstance(first, (WinogradConv3x3BiasAct, StridedConv3x3BiasAct)) else None
+        if first_path == 'k21':
+            # (fold_batchnorm(split3x3=True)) K21 applies the 3x3 layer's own epilogue; the project is then an ordinary
+            # call (K13, or K20 under split_gemm; no prologue) with the skip
+            self.last_path = 'k21'
+            return project(first(x), residual=residual)
+        if first_path == 'k19':
             # K19 applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
             # split_gemm; no prologue) with the skip
             self.last_path = 'k19'
             return project(first(x), residual=residual)
-        if isinstance(first, StridedConv3x3BiasAct) and first.path(x) == 'k22':
+        if first_path == 'k22':
             # the same for a stride-2 expand: K22 with the layer's own epilogue, then the project as an ordinary call
             self.last_path = 'k22'
             return project(first(x), residual=residual)
@@ -887,6 +893,77 @@ class WinogradConv3x3BiasAct(ConvBiasAct):
         return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
 
 
+class SplitConv3x3BiasAct(WinogradConv3x3BiasAct):
+    """A folded dense 3x3, stride-1, padding-1 conv + BN (+ activation) with Cin % 8 == 0 of an f32 copy made with
+    fold_batchnorm(split3x3=True): the convolution on the bf16 matrix cores from operands split into three bf16 pieces
+    each (K20's arithmetic), "+ bias", the activation and the block's skip as ONE HIP launch (K21, conv3x3_split.hip)
+    instead of a MIOpen convolution followed by K10.  Same parameters and state_dict keys as the ConvBiasAct it
+    replaces (the split weight is derived state, cached per weight storage and version).  It derives from
+    WinogradConv3x3BiasAct so that one layer can hold both options: `winograd` says whether winograd3x3 was on too.
+    Where K21 refuses the input or lists the shape, the layer runs K19 if `winograd` and K19 takes it, and exactly what
+    ConvBiasAct runs everywhere else -- CPU, channels_last, autocast, a gradient wanted, W % 4 != 0."""
+
+    # class-wide switch (tests and A/B runs): what the copy without split3x3 runs, everywhere
+    use_k21 = True
+    # (Cin, Cout, H, W) of the input where K21 (for the expand of a FusedMBConv: K21 + the plain K13 project) was not
+    # ahead of the default copy's path in every round of tools/conv3x3_ab.py --dtype f32 (EfficientNetV2-S and ResNet-18
+    # batch 64 at 256 px, EfficientNetV2-L batch 32 at 384 px; DESIGN.md section 34,
+    # profiles/r25a_conv3x3_ab_k21_*.jsonl): the small maps of ResNet-18 -- one tile per image on 16x16 maps (at batch
+    # 64 fewer workgroups than CUs), a quarter of a tile on 8x8 maps
+    k21_slower = frozenset({(256, 256, 16, 16), (512, 512, 8, 8)})
+
+    def __init__(self, conv, bias, act, winograd=False):
+        super().__init__(conv, bias, act)  # (last_path: 'k21', 'k19' or 'library')
+        self.winograd = bool(winograd)
+        self._w3s = None
+
+    @staticmethod
+    def applies_to(conv):
+        return _dense_3x3(conv, strides=((1, 1),)) and conv.in_channels % 8 == 0
+
+    def weight_split3(self):
+        """The conv's weight split for K21 ([3, Cout, 3, 3, Cp] bf16, kernels.pack_conv3x3_split_weight): made on the
+        first K21 forward and kept as _derived_weight says."""
+        self._w3s = _derived_weight(self._w3s, self.conv.weight, kernels.pack_conv3x3_split_weight)
+        return self._w3s[1]
+
+    def k19_takes(self, x):
+        """K19 only where winograd3x3 was on as well."""
+        return self.winograd and super().k19_takes(x)
+
+    def k21_takes(self, x):
+        """Whether forward(x) runs on K21: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
+        the C entry accepts and that is not listed as slower."""
+        c = self.conv
+        if not (SplitConv3x3BiasAct.use_k21 and not self.emit_mean and x.is_cuda and x.dim() == 4
+                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
+                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
+                and _inference_call(c.weight, x=x)):
+            return False
+        B, K, H, W = x.shape
+        if K != c.in_channels or (K, c.out_channels, H, W) in SplitConv3x3BiasAct.k21_slower:
+            return False
+        return _lib.load().mtr_conv3x3_split_lds_bytes(B, K, c.out_channels, H, W) > 0
+
+    def path(self, x, residual=None, pre=None, defer_epilogue=False):
+        """'k21' in front of WinogradConv3x3BiasAct's order ('k19' where winograd3x3 armed it too, then ConvBiasAct's,
+        which for a 3x3 layer says 'library')."""
+        if not defer_epilogue and pre is None and self.k21_takes(x) and _addable(
+                residual, x, shape=(x.shape[0], self.conv.out_channels) + x.shape[2:]):
+            return 'k21'
+        return super().path(x, residual, pre, defer_epilogue)
+
+    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
+        path = self.path(x, residual, pre, defer_epilogue)
+        if path == 'k21':
+            self.last_path = 'k21'
+            return kernels.conv3x3_bias_act_split(x, self.weight_split3(), self.bias, self.act_name, residual=residual)
+        if path == 'k19':
+            self.last_path = 'k19'
+            return kernels.conv3x3_winograd_bias_act(x, self.weight_u(), self.bias, self.act_name, residual=residual)
+        return ConvBiasAct.forward(self, x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+
+
 class StridedConv3x3BiasAct(ConvBiasAct):
     """A folded dense 3x3, stride-2, padding-1 conv + BN (+ activation) with Cin % 4 == 0 of an f32 copy made with
     fold_batchnorm(strided3x3=True): the convolution as an implicit GEMM on the f32 MFMA, "+ bias" and the activation
@@ -1252,6 +1329,20 @@ def _replace_winograd(folded):
     _replace_conv_bias_act(folded, WinogradConv3x3BiasAct)
 
 
+def _replace_split3x3(folded, winograd3x3):
+    """split3x3: every dense 3x3, stride-1, padding-1, ungrouped ConvBiasAct with Cin % 8 == 0 that emits no mean
+    becomes a SplitConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L, 13 of ResNet-18, none of MobileNetV3.  Such
+    a layer runs on the bf16 matrix cores from split operands, with "+ bias", the activation and the block's skip in
+    one launch (K21, .last_path 'k21') where that kernel takes the input and the shape is not in
+    SplitConv3x3BiasAct.k21_slower.  Everywhere else it runs what the copy without split3x3 runs: K19 where
+    `winograd3x3` is on as well and K19 takes the tensor ('k19'), else exactly what ConvBiasAct runs.  An armed
+    FusedMBConv expand block runs K21 with its own epilogue and then the project as a plain K13 call -- a plain K20
+    call with split_gemm=True -- (block .last_path 'k21').  f32-grade against fp64 but not the library's bits.  Runs
+    in front of _replace_winograd, which then finds these layers taken."""
+    for blk in _replace_conv_bias_act(folded, SplitConv3x3BiasAct):
+        blk[0].winograd = bool(winograd3x3)
+
+
 def _replace_strided3x3(folded):
     """strided3x3: every dense 3x3, stride-2, padding-1, ungrouped ConvBiasAct with Cin % 4 == 0 that emits no mean
     becomes a StridedConv3x3BiasAct: 2 layers of EfficientNetV2-S, 2 of -L, 3 of ResNet-18, none of MobileNetV3 (the
@@ -1265,12 +1356,13 @@ def _replace_strided3x3(folded):
 
 
 def _arm_pre_pairs(folded):
-    """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the WinogradConv3x3BiasAct
-    or StridedConv3x3BiasAct that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
+    """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the WinogradConv3x3BiasAct,
+    SplitConv3x3BiasAct or StridedConv3x3BiasAct that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
     and applied by the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with
     the bits of the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict."""
     for m in folded.modules():
-        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct, StridedConv3x3BiasAct))
+        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct, SplitConv3x3BiasAct,
+                                       StridedConv3x3BiasAct))
         if pair:
             m.pre_pair = pair
 
@@ -1379,14 +1471,14 @@ _NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
           'f32': (lambda fused, dtype: fused and dtype is None, 'fused_epilogue=True and an f32 copy (no dtype=)')}
 _OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
                  ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'),
-                 ('strided3x3', 'f32'), ('fuse_expand_depthwise', '16bit'),
+                 ('strided3x3', 'f32'), ('split3x3', 'f32'), ('fuse_expand_depthwise', '16bit'),
                  ('fuse_expand_depthwise_planes', '16bit'), ('fuse_expand_depthwise_tiles', '16bit'))
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                    block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
                    strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False,
-                   fuse_expand_depthwise_tiles=False):
+                   fuse_expand_depthwise_tiles=False, split3x3=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -1411,6 +1503,10 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     split_gemm=True (needs fused_epilogue=True and an f32 copy): the f32 1x1 layers on K20 (_arm_split_gemm).
     strided3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-2 layers with Cin % 4 == 0 as an
     implicit GEMM on the f32 MFMA, K22 (_replace_strided3x3).
+    split3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-1 layers with Cin % 8 == 0 on the
+    bf16 matrix cores by operand split, K21 (_replace_split3x3).  Together with winograd3x3 the layers are
+    SplitConv3x3BiasAct and run K21 where it takes the tensor, K19 where K21 refuses or lists the shape and K19 takes
+    it, the library path otherwise.
     fuse_expand_depthwise=True (needs a 16-bit dtype): the 1x1 expand and the stride-1 depthwise 3x3 layer of an MBConv
     block as one launch, K25h (_arm_expand_depthwise).
     fuse_expand_depthwise_planes=True (needs a 16-bit dtype): the same pairs as one launch on the planes K25h refuses
@@ -1418,7 +1514,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     fuse_expand_depthwise_tiles=True (needs a 16-bit dtype): the same pairs and the stride-2 pairs without a folded
     padding as one launch on the large planes of the layers that emit no mean (64x64, 128x128 -> 64x64, 32x32 -> 16x16 of
     MobileNetV3), K27h (_arm_expand_depthwise on hand_tiles_to).
-    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3; 16-bit:
+    The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3, split3x3; 16-bit:
     fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise, fuse_expand_depthwise_planes, fuse_expand_depthwise_tiles): no two of them arm the same field of the same module, and
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
@@ -1438,7 +1534,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                    deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
                    strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise,
                    fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
-                   fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles)
+                   fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3)
     for option, need in _OPTION_NEEDS:
         met, text = _NEEDS[need]
         if options[option] and not met(fused_epilogue, dtype):
@@ -1448,6 +1544,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     if fused_epilogue:
         _fold_paddings(folded)
         _wire_squeeze_excite(folded)
+    if split3x3:
+        _replace_split3x3(folded, winograd3x3)
     if winograd3x3:
         _replace_winograd(folded)
     if strided3x3:

@@ -1384,3 +1384,82 @@ def conv1x1_bias_act_split(x, w_split, bias, act, gate=None, residual=None, in_b
         None if gate is None else _ptr(gate.contiguous()), None if residual is None else _ptr(residual),
         ACT_CODES[act], B, M, K, H * W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv1x1_bias_act_split')
     return out
+
+
+# K21: a dense 3x3 stride-1 convolution of f32 tensors on the bf16 matrix cores, from operands split into three bf16
+# pieces (csrc/conv3x3_split.hip)
+
+CONV3X3_SPLIT_CHUNK = 16   # input channels per k step of K21: Cp of the packed weight is Cin rounded up to this
+
+
+def pack_conv3x3_split_weight(weight):
+    """The [Cout, Cin, 3, 3] f32 convolution weight as mtr_conv3x3_bias_act_split takes it: [3, Cout, 3, 3, Cp] bf16,
+    contiguous, ci innermost, Cp = Cin rounded up to 16 with a zero tail; piece 0 = bf16_rn(w), piece 1 = bf16_rn(w -
+    p0), piece 2 = bf16_rn(w - p0 - p1).  The subtractions are exact in f32 and p0 + p1 + p2 == w bit for bit
+    (asserted) for finite weights whose third piece does not underflow.  Plain torch; done once per weight."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] % 8:
+        raise ValueError(f'pack_conv3x3_split_weight: expected [Cout, Cin, 3, 3] with Cin a multiple of 8, '
+                         f'got {tuple(weight.shape)}')
+    if weight.dtype != torch.float32:
+        raise ValueError(f'pack_conv3x3_split_weight: expected an f32 weight, got {weight.dtype}')
+    w = weight.detach().permute(0, 2, 3, 1)   # [Cout, 3, 3, Cin]
+    M, K = weight.shape[:2]
+    w0 = w.to(torch.bfloat16)
+    r1 = w - w0.float()
+    w1 = r1.to(torch.bfloat16)
+    r2 = r1 - w1.float()
+    w2 = r2.to(torch.bfloat16)
+    if not torch.equal(w0.float() + w1.float() + w2.float(), w):
+        raise AssertionError('pack_conv3x3_split_weight: the three bf16 pieces do not sum back to the weight '
+                             '(non-finite or subnormal-range values)')
+    Kp = (K + CONV3X3_SPLIT_CHUNK - 1) // CONV3X3_SPLIT_CHUNK * CONV3X3_SPLIT_CHUNK
+    out = torch.zeros(3, M, 3, 3, Kp, dtype=torch.bfloat16, device=w.device)
+    out[0, ..., :K], out[1, ..., :K], out[2, ..., :K] = w0, w1, w2
+    return out
+
+
+def _conv3x3_split_weight_fits(w_split, K):
+    return w_split.dim() == 5 and w_split.dtype == torch.bfloat16 and w_split.shape[0] == 3 \
+        and tuple(w_split.shape[2:4]) == (3, 3) and K % 8 == 0 \
+        and w_split.shape[4] == (K + CONV3X3_SPLIT_CHUNK - 1) // CONV3X3_SPLIT_CHUNK * CONV3X3_SPLIT_CHUNK \
+        and w_split.is_contiguous()
+
+
+def conv3x3_split_supported(x, w_split):
+    """Whether mtr_conv3x3_bias_act_split takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
+    aligned, w_split [3, Cout, 3, 3, Cp] bf16 contiguous (pack_conv3x3_split_weight), Cin a multiple of 8, W a multiple
+    of 4 (its MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not w_split.is_cuda or not x.is_contiguous() \
+            or x.data_ptr() % 16 or w_split.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    if not _conv3x3_split_weight_fits(w_split, K):
+        return False
+    return _lib.load().mtr_conv3x3_split_lds_bytes(B, K, w_split.shape[1], H, W) > 0
+
+
+def conv3x3_bias_act_split(x, w_split, bias, act, residual=None, out=None):
+    """y = act(conv3x3(x, w, stride 1, padding 1) + bias) (+ residual) in one launch on the current stream, for f32
+    tensors on the bf16 matrix cores (K21): x [B, Cin, H, W] NCHW-contiguous, w_split [3, Cout, 3, 3, Cp] bf16
+    (pack_conv3x3_split_weight), bias [Cout] f32, residual [B, Cout, H, W] f32 or None (it may be x).  The f32 product
+    is summed from six bf16 products of the split operands in a fixed order: f32-grade against fp64, the same bits on
+    every call and graph replay, for any batch size, but not the bits of the library's convolution."""
+    require_cuda(x, w_split, bias, residual)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('conv3x3_bias_act_split: x must be [B, Cin, H, W] f32, NCHW-contiguous')
+    B, K, H, W = x.shape
+    if not _conv3x3_split_weight_fits(w_split, K):
+        raise ValueError(f'conv3x3_bias_act_split: the weight must be split [3, Cout, 3, 3, Cp] bf16 and contiguous '
+                         f'for {K} input channels (a multiple of 8), got {tuple(w_split.shape)} {w_split.dtype}')
+    M = w_split.shape[1]
+    if bias.numel() != M:
+        raise ValueError(f'conv3x3_bias_act_split: bias has {bias.numel()} elements, expected {M}')
+    out = _residual_and_out('conv3x3_bias_act_split', x, (B, M, H, W), residual, out)
+    for t, name in ((x, 'x'), (residual, 'residual')):
+        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
+                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError(f'conv3x3_bias_act_split: out must not overlap {name}')
+    check(_lib.load().mtr_conv3x3_bias_act_split(
+        _ptr(x), _ptr(w_split), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3_bias_act_split')
+    return out

@@ -57,7 +57,7 @@ def load_joint_info(model_dir):
 def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
                     fuse_blocks=False, fuse_stem=False, block_depthwise=False, deep_projects=False,
                     winograd3x3=False, split_gemm=False, strided3x3=False, fuse_expand_depthwise=False,
-                    fuse_expand_depthwise_planes=False, fuse_expand_depthwise_tiles=False):
+                    fuse_expand_depthwise_planes=False, fuse_expand_depthwise_tiles=False, split3x3=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
@@ -88,6 +88,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     copy's dense 3x3 stride-2 layers with Cin % 4 == 0 as an implicit GEMM on the f32 MFMA with their epilogue folded in
     (backbones.fold_batchnorm(strided3x3=True), K22): equal to the default copy up to rounding.  Like fuse_stem it
     always gives the folded copy with fused epilogues.
+    split3x3=True (an f32 copy only, else ValueError; off by default; independent of the other options) runs the
+    copy's dense 3x3 stride-1 layers with Cin % 8 == 0 on the bf16 matrix cores from operands split into three bf16
+    pieces, with their epilogue folded in (backbones.fold_batchnorm(split3x3=True), K21): f32-grade, equal to the
+    default copy up to rounding.  With winograd3x3=True as well, K19 serves what K21 leaves.  Like fuse_stem it always
+    gives the folded copy with fused epilogues.
     fuse_expand_depthwise=True (a 16-bit dtype only, else ValueError; off by default) runs the 1x1 expand and the
     stride-1 depthwise 3x3 layer of the copy's MBConv blocks as one launch each
     (backbones.fold_batchnorm(fuse_expand_depthwise=True), K25h): the same bits.
@@ -120,6 +125,8 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
         raise ValueError('load_crop_model: split_gemm=True needs an f32 copy (dtype=None or torch.float32)')
     if strided3x3 and dtype is not None:
         raise ValueError('load_crop_model: strided3x3=True needs an f32 copy (dtype=None or torch.float32)')
+    if split3x3 and dtype is not None:
+        raise ValueError('load_crop_model: split3x3=True needs an f32 copy (dtype=None or torch.float32)')
     cfg, raw = load_config(model_dir)
     # config.affine_weights (models/metrabs.py:23-32) is a path or a name under $DATA_ROOT/skeleton_conversion;
     # a file of that name shipped INSIDE the model directory is found too
@@ -142,11 +149,11 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
                               fuse_expand_depthwise=fuse_expand_depthwise,
                               fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
                               fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles)
-    elif fuse_stem or block_depthwise or winograd3x3 or split_gemm or strided3x3:
+    elif fuse_stem or block_depthwise or winograd3x3 or split_gemm or strided3x3 or split3x3:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=fuse_stem,
                               block_depthwise=block_depthwise, winograd3x3=winograd3x3, split_gemm=split_gemm,
-                              strided3x3=strided3x3)
+                              strided3x3=strided3x3, split3x3=split3x3)
     elif fold_batchnorm:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=fused_epilogue)
@@ -157,9 +164,9 @@ def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchno
                            fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                            block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
                            strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False,
-                           fuse_expand_depthwise_tiles=False):
+                           fuse_expand_depthwise_tiles=False, split3x3=False):
     """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise, deep_projects,
-    winograd3x3, split_gemm, strided3x3, fuse_expand_depthwise, fuse_expand_depthwise_planes,
+    winograd3x3, split_gemm, strided3x3, split3x3, fuse_expand_depthwise, fuse_expand_depthwise_planes,
     fuse_expand_depthwise_tiles:
     as load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
     model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
@@ -167,7 +174,7 @@ def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchno
                             deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
                             strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise,
                             fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
-                            fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles)
+                            fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

@@ -38,6 +38,10 @@ ab='k20' and the paths of the 1x1 layers of both arms.
 strided3x3=True (the dense 3x3 stride-2 layers on K22 where StridedConv3x3BiasAct.k22_slower does not list them);
 --winograd3x3 folds BOTH arms with winograd3x3=True as well.  The arms differ by rounding; the rows carry ab='k22', the
 paths of the armed layers and the MPJPE between the two arms' poses.
+--ab k21: both arms are the f32 copy of the same network (--dtype f32; --config 1), A folded as by default, B with
+split3x3=True (the dense 3x3 stride-1 layers on K21 where SplitConv3x3BiasAct.k21_slower does not list them);
+--winograd3x3 folds BOTH arms with winograd3x3=True as well (B then runs K19 where K21 leaves a layer).  The arms differ
+by rounding; the rows carry ab='k21', the paths of the armed layers and the MPJPE between the two arms' poses.
 --ab k27h: both arms are the 16-bit copy of the same network (--config 3, MobileNetV3), A folded as by default, B with
 fuse_expand_depthwise_tiles=True (the expand + depthwise 3x3 pairs on large planes as one launch, K27h, where
 DepthwiseBiasAct.k27h_slower does not list them).  The rows carry ab='k27h' and the paths of the armed expands.
@@ -60,14 +64,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
-    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k22', 'k25h',
-                                     'k26h', 'k27h'],
+    ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k21', 'k22',
+                                     'k25h', 'k26h', 'k27h'],
                     default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
                          "k18: without vs with block_depthwise; deepk: without vs with deep_projects; "
                          "k19 (--dtype f32): the f32 copy folded without vs with winograd3x3; "
                          "k20 (--dtype f32): the f32 copy folded without vs with split_gemm; "
+                         "k21 (--dtype f32): the f32 copy folded without vs with split3x3; "
                          "k22 (--dtype f32): the f32 copy folded without vs with strided3x3; "
                          "k25h: the 16-bit copy folded without vs with fuse_expand_depthwise; "
                          "k26h: the 16-bit copy folded without vs with fuse_expand_depthwise_planes (--config 4, or "
@@ -76,17 +81,17 @@ def main():
     ap.add_argument('--res', type=int, default=None, help='crop side handed to bench.py (its --res) instead of the '
                                                           "config's own")
     ap.add_argument('--winograd3x3', action='store_true',
-                    help='--ab k20, --ab k22: fold both arms with winograd3x3=True too')
+                    help='--ab k20, --ab k21, --ab k22: fold both arms with winograd3x3=True too')
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
-    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19', 'k20', 'k22') \
+    if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19', 'k20', 'k21', 'k22') \
             and not (args.ab == 'k27h' and args.dtype != 'f32'):
-        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18, --ab k19, --ab k20 or --ab k22 '
+        ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18, --ab k19, --ab k20, --ab k21 or --ab k22 '
                  '(--config 3 with a 16-bit dtype also with --ab k27h)')
-    if args.ab in ('k19', 'k20', 'k22') and args.dtype != 'f32':
+    if args.ab in ('k19', 'k20', 'k21', 'k22') and args.dtype != 'f32':
         ap.error(f'--ab {args.ab} goes with --dtype f32')
-    if args.winograd3x3 and args.ab not in ('k20', 'k22'):
-        ap.error('--winograd3x3 goes with --ab k20 or --ab k22')
+    if args.winograd3x3 and args.ab not in ('k20', 'k21', 'k22'):
+        ap.error('--winograd3x3 goes with --ab k20, --ab k21 or --ab k22')
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -146,6 +151,16 @@ def main():
             e.crop_dtype = e.crop_model.input_dtype
             e.crop_model.autocast_dtype = None                   # f32 copies, run in f32
         assert any(isinstance(m, ConvBiasAct) and m.split_gemm for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k21':                                         # both arms the f32 copy, B with K21 armed
+        from metrabs_amd.backbones import SplitConv3x3BiasAct
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True,
+                                                   winograd3x3=args.winograd3x3)
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True,
+                                                   winograd3x3=args.winograd3x3, split3x3=True)
+        for e in (est_a, est_b):
+            e.crop_dtype = e.crop_model.input_dtype
+            e.crop_model.autocast_dtype = None                   # f32 copies, run in f32
+        assert any(isinstance(m, SplitConv3x3BiasAct) for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k22':                                         # both arms the f32 copy, B with K22 armed
         from metrabs_amd.backbones import StridedConv3x3BiasAct
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True,
@@ -302,6 +317,14 @@ def main():
                    mpjpe_armed_vs_default_mm=round(float((p_b - p_a).norm(dim=-1).mean()), 5),
                    a={str(k): paths[0].count(k) for k in sorted(set(paths[0]), key=str)},
                    b={str(k): paths[1].count(k) for k in sorted(set(paths[1]), key=str)})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k21':
+        from metrabs_amd.backbones import SplitConv3x3BiasAct
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules() if isinstance(m, SplitConv3x3BiasAct)]
+        row = dict(kind='paths', ab='k21', winograd3x3=args.winograd3x3,
+                   mpjpe_armed_vs_default_mm=round(float((p_b - p_a).norm(dim=-1).mean()), 5),
+                   b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
         print(json.dumps(row), flush=True)
         rows.append(row)
     if args.ab == 'k22':

@@ -66,7 +66,7 @@ def record(args):
                          dtype=dt if args.precision.endswith('-copy') else None, fuse_blocks=args.fuse_blocks,
                          fuse_stem=args.fuse_stem, block_depthwise=args.block_depthwise,
                          winograd3x3=args.winograd3x3, split_gemm=args.split_gemm, strided3x3=args.strided3x3,
-                         deep_projects=args.deep_projects)
+                         deep_projects=args.deep_projects, split3x3=args.split3x3)
     x = torch.rand(args.batch, 3, args.res, args.res, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     if dt is not None:
         x = x.to(dt)   # the sampler writes 16-bit crops in both 16-bit modes
@@ -138,6 +138,8 @@ def _kind(kname):
         return 'K16h'
     if 'conv3x3s2_kernel' in k:  # K22 (before the generic 'conv' match): the f32 dense 3x3 stride-2 conv + epilogue
         return 'K22'
+    if 'conv3x3_split_kernel' in k:  # K21 (before the generic 'conv' match): the f32 dense 3x3 conv on the bf16 matrix cores
+        return 'K21'
     if 'conv3x3_winograd_kernel' in k:  # K19 (before the generic 'conv' match): the f32 dense 3x3 Winograd conv + epilogue
         return 'K19'
     if 'conv3x3_16_kernel' in k:  # K14h (before the generic 'conv' match): the 16-bit dense 3x3 conv + epilogue
@@ -213,19 +215,19 @@ def _fused_table(per_kernel, pat):
             continue
         b = rows.setdefault(key, defaultdict(float))
         if layer == 0:
-            col = kind if kind in ('K14h', 'K19', 'K22', 'K10') else 'dense conv'
+            col = kind if kind in ('K14h', 'K19', 'K21', 'K22', 'K10') else 'dense conv'
             if col == 'dense conv' and key != 'stem':
                 served[f'{kind}: {kname[:60]}'] += us
         else:
             col = 'project'   # (K13 / K13h / K20, or the library GEMM + K10)
         b[col] += us
-    cols = ['dense conv', 'K14h', 'K19', 'K22', 'K10', 'project', 'K16h']
+    cols = ['dense conv', 'K14h', 'K19', 'K21', 'K22', 'K10', 'project', 'K16h']
     lines = ['', '## FusedMBConv stages and the stem: the dense 3x3 layer, the K10 pass behind it, the 1x1 project '
                  '(or K16h: all of them in one launch)', '',
              '| stage.block | ' + ' | '.join(cols) + ' | **3x3 + K10** |', '|---|' + '---|' * (len(cols) + 1)]
     sums = defaultdict(float)
     for key, b in rows.items():
-        dense = b['dense conv'] + b['K14h'] + b['K19'] + b['K22'] + b['K10']
+        dense = b['dense conv'] + b['K14h'] + b['K19'] + b['K21'] + b['K22'] + b['K10']
         for c in cols:
             sums[c] += b[c]
         sums['dense'] += dense
@@ -235,7 +237,7 @@ def _fused_table(per_kernel, pat):
     lines.append('| **sum** | ' + ' | '.join(f'{sums[c]:.1f}' for c in cols) + f' | **{sums["dense"]:.1f}** |')
     lines += ['', f'Dense 3x3 layers of stages 1 - 3 with their epilogue (without the stem): '
                   f'**{sums["dense_blocks"]:.1f} us**.']
-    slice23 = sum(b['dense conv'] + b['K14h'] + b['K19'] + b['K22'] + b['K10'] + b['project'] + b['K16h']
+    slice23 = sum(b['dense conv'] + b['K14h'] + b['K19'] + b['K21'] + b['K22'] + b['K10'] + b['project'] + b['K16h']
                   for key, b in rows.items() if key.split('.')[0] in ('2', '3'))
     lines += ['', f'Dense 3x3 + project of stages 2 - 3 (K16h included): **{slice23:.1f} us**.']
     if served:
@@ -375,6 +377,9 @@ def main():
                    help='fold with winograd3x3=True (f32 only): the dense 3x3 stride-1 layers on K19')
     r.add_argument('--strided3x3', action='store_true',
                    help='fold with strided3x3=True (f32 only): the dense 3x3 stride-2 layers (Cin a multiple of 4) on K22')
+    r.add_argument('--split3x3', action='store_true',
+                   help='fold with split3x3=True (f32 only): the dense 3x3 stride-1 layers (Cin a multiple of 8) on K21, '
+                        'the split-operand kernel')
     r.add_argument('--split-gemm', action='store_true',
                    help='fold with split_gemm=True (f32 only): the 1x1 stride-1 layers on K20, the split-operand kernel')
     r.add_argument('--deep-projects', action='store_true',

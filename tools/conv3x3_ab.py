@@ -25,6 +25,10 @@ The stride-2 classes of the copy folded with strided3x3=True are timed in the sa
 (kernels.conv3x3_strided_bias_act) in the place of K19: a FusedMBConv expand as the pair (MIOpen pinned + K13 with the
 prologue against K22 + the plain K13 call), a ResNet layer alone against MIOpen + K10; their records say stride 2 and
 k22_*, and the share of the matrix peak is counted in direct-convolution FLOP.
+The stride-1 classes with Cin % 8 == 0 get a THIRD arm in the same rounds, K21 (kernels.conv3x3_bias_act_split: the
+f32 product on the bf16 matrix cores by operand split) in the place of K19 -- a layer as a layer, a FusedMBConv expand
+as the pair K21 + the plain K13 call: k21_us, its rounds, whether it is ahead of the default arm and of K19 in every
+round, and (a layer alone) the share of the 2.5 PF bf16 peak its six piece products reach.
 """
 import argparse
 import json
@@ -114,6 +118,9 @@ def main_f32(args):
         b = torch.randn(M, device='cuda', generator=g)
         y = torch.empty(B, M, Ho, Wo, device='cuda')
         supported = takes(x, wu)
+        # the third arm of a stride-1 class: K21
+        w21 = kernels.pack_conv3x3_split_weight(w) if stride == 1 and K % 8 == 0 else None
+        third = w21 is not None and kernels.conv3x3_split_supported(x, w21)
         if P is None:
             r = torch.randn(B, M, Ho, Wo, device='cuda', generator=g) if skip else None
 
@@ -124,6 +131,9 @@ def main_f32(args):
 
             def new():
                 return conv(x, wu, b, act, residual=r, out=y)
+
+            def new21():
+                return kernels.conv3x3_bias_act_split(x, w21, b, act, residual=r, out=y)
         else:
             w1 = torch.randn(P, M, 1, 1, device='cuda', generator=g) / M ** 0.5
             b1 = torch.randn(P, device='cuda', generator=g)
@@ -135,6 +145,10 @@ def main_f32(args):
 
             def new():
                 conv(x, wu, b, act, out=y)
+                return kernels.conv1x1_bias_act(y, w1, b1, None, residual=r)
+
+            def new21():
+                kernels.conv3x3_bias_act_split(x, w21, b, act, out=y)
                 return kernels.conv1x1_bias_act(y, w1, b1, None, residual=r)
 
         def captured(fn):
@@ -166,22 +180,34 @@ def main_f32(args):
                 c = new()
                 torch.cuda.synchronize()
                 diff = float((a - c).abs().max() / a.abs().max().clamp_min(1e-30))
+            diff21 = None
+            if third:
+                c = new21()
+                torch.cuda.synchronize()
+                diff21 = float((a - c).abs().max() / a.abs().max().clamp_min(1e-30))
             for _ in range(3):
                 old()
                 if supported:
                     new()
+                if third:
+                    new21()
             arm_old = captured(old)
             arm_new = captured(new) if supported else None
+            arm_21 = captured(new21) if third else None
             for _ in range(2):
                 timed(arm_old)
                 if supported:
                     timed(arm_new)
-            t_old, t_new = [], []
+                if third:
+                    timed(arm_21)
+            t_old, t_new, t_21 = [], [], []
             for _ in range(args.rounds):
                 t_old.append(timed(arm_old))
                 if supported:
                     t_new.append(timed(arm_new))
-            del arm_old, arm_new
+                if third:
+                    t_21.append(timed(arm_21))
+            del arm_old, arm_new, arm_21
         direct_flop = 2.0 * B * Ho * Wo * 9 * K * M
         # what the new arm's MFMAs compute: the Winograd-domain products of K19, the direct convolution of K22
         wino_flop = 2.0 * B * (H // 2) * (W // 2) * 16 * K * M if stride == 1 else direct_flop
@@ -202,6 +228,13 @@ def main_f32(args):
                 row.update({tag + ('_winograd_tflops' if stride == 1 else '_direct_tflops'): round(wino_flop / t / 1e6, 1),
                             tag + '_share_of_f32_peak': round(wino_flop / t / 1e6 / PEAK32_TF, 3)},
                            share_of_byte_floor=round(byte_floor / t, 3))
+        if third:
+            t = med(t_21)
+            row.update(k21_us=round(t, 2), k21_us_rounds=[round(v, 2) for v in t_21],
+                       k21_ahead_in_every_round=max(t_21) < min(t_old), k21_speedup=round(med(t_old) / t, 3),
+                       k21_ahead_of_k19_in_every_round=bool(t_new) and max(t_21) < min(t_new), k21_rel_diff=diff21)
+            if P is None:   # six bf16 piece products of the direct convolution
+                row.update(k21_share_of_bf16_peak=round(6 * direct_flop / t / 1e6 / PEAK16_TF, 3))
         rows.append(row)
         print(json.dumps(row), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
