@@ -222,11 +222,37 @@ def crop_geometry(boxes, intrinsics, distortion12, camspace_up, image_ids, aug_r
     return new_k, rot, wp
 
 
+# bytes of res*aa crops the antialias > 4 path holds at a time (_warp_crops_big_antialias)
+MAX_BIG_CROP_BYTES = 1 << 30
+
+
+def _check_warp_args(pyramid, warp_params, res, out_dtype, channels_last, out):
+    """What warp_crops asks of its rows and of a caller's `out` (the kernels read 36 consecutive floats per crop and
+    write a dense crop-major buffer: anything else would be sampled or written as garbage, silently)."""
+    if not isinstance(warp_params, torch.Tensor) or not warp_params.is_cuda:
+        raise ValueError('warp_crops: warp_params must be on the GPU')
+    if warp_params.dtype != torch.float32 or warp_params.ndim != 2 or \
+            warp_params.shape[1] != _lib.MTR_WARP_PARAM_FLOATS or not warp_params.is_contiguous():
+        raise ValueError(f'warp_crops: warp_params must be float32 [n, {_lib.MTR_WARP_PARAM_FLOATS}], contiguous')
+    if warp_params.device != pyramid.device:
+        raise ValueError('warp_crops: warp_params and the pyramid are on different devices')
+    if out is None:
+        return
+    n, res = warp_params.shape[0], int(res)
+    ok = isinstance(out, torch.Tensor) and out.shape == (n, 3, res, res) and out.dtype == out_dtype and \
+        out.device == warp_params.device
+    # (the memory order asked for, crop-major and dense)
+    if not ok or not (out.permute(0, 2, 3, 1) if channels_last else out).is_contiguous():
+        layout = 'over [n, res, res, 3] memory (channels_last)' if channels_last else 'contiguous'
+        raise ValueError(f'warp_crops: out must be {out_dtype} [n, 3, res, res] {layout} on the rows\' device')
+
+
 def warp_crops(pyramid, warp_params, res, antialias=1, out_dtype=torch.float32,
                channels_last=False, out=None):
     """Pyramid + [n,36] warp rows -> crops [n,3,res,res] (NCHW) or NHWC memory when
-    channels_last (returned as a logically-NCHW channels_last tensor)."""
-    require_cuda(warp_params)
+    channels_last (returned as a logically-NCHW channels_last tensor).  warp_params: float32 [n,36] contiguous on
+    the pyramid's device; out (optional): [n,3,res,res] of out_dtype in the layout asked for -- ValueError otherwise."""
+    _check_warp_args(pyramid, warp_params, res, out_dtype, channels_last, out)
     n = warp_params.shape[0]
     dev = warp_params.device
     if antialias > 4:
@@ -258,7 +284,7 @@ def _warp_crops_big_antialias(pyramid, warp_params, res, antialias, out_dtype, c
     """antialias_factor > 4 (multiperson_model.py:312-315): sample at res*aa x res*aa in linear light
     (gamma exponent 1), shrink with aten's antialiased separable bilinear filter + the per-crop gamma
     (mtr_crops_shrink_antialiased).  The res*aa crops are 3 * (res*aa)^2 * 4 bytes each (50 MB at
-    256 px, aa = 8): they are produced and consumed in chunks of <= 1 GiB."""
+    256 px, aa = 8): they are produced and consumed in chunks of <= MAX_BIG_CROP_BYTES (1 GiB)."""
     lib = _lib.load()
     n, dev = warp_params.shape[0], warp_params.device
     if 2 * antialias + 2 > 40:
@@ -270,7 +296,7 @@ def _warp_crops_big_antialias(pyramid, warp_params, res, antialias, out_dtype, c
     wp_lin = warp_params.clone()
     wp_lin[:, 33] = 1.0
     per = 3 * big * big * 4
-    chunk = max(1, min(n, (1 << 30) // per))
+    chunk = max(1, min(n, MAX_BIG_CROP_BYTES // per))
     flat_out = out.permute(0, 2, 3, 1) if channels_last else out  # the memory order, crop-major
     for a in range(0, n, chunk):
         b = min(n, a + chunk)

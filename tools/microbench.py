@@ -146,7 +146,7 @@ def bench_warp_pyramid():
         tg = timeit(geo)
         _, _, wp = geo()
         o = torch.empty(n * num_aug, 3, 256, 256, device='cuda', dtype=dt)
-        t = timeit(lambda: kernels.warp_crops(pyr, wp, 256, aa, out=o))
+        t = timeit(lambda: kernels.warp_crops(pyr, wp, 256, aa, out_dtype=dt, out=o))
         nbytes = o.numel() * o.element_size()
         # algorithmic bytes = the crops written + the clipped source footprint of every crop quad
         # (bench.source_footprint_bytes); the same 8 frames every launch, i.e. the
@@ -157,7 +157,7 @@ def bench_warp_pyramid():
                         out_GBps=round(nbytes / t / 1e9, 1), crops_per_s=round(n * num_aug / t),
                         algorithmic_MB=round((nbytes + src) / 1e6, 1),
                         frac_hbm_cache_assisted=round((nbytes + src) / t / HBM, 3)))
-        t_il = timeit(lambda: kernels.warp_crops(pyr_il, wp, 256, aa, out=o))
+        t_il = timeit(lambda: kernels.warp_crops(pyr_il, wp, 256, aa, out_dtype=dt, out=o))
         out[-1]['interleaved_frames_us'] = round(t_il * 1e6, 1)
     return out
 
