@@ -877,6 +877,38 @@ int mtr_expand_dw16_tiles(const void* x, int dtype, const void* w1 /*[Cmid][Cin]
  * MTR_E_SHAPE (and for B <= 0).  No GPU work. */
 size_t mtr_expand_dw16_tiles_lds_bytes(long long B, int Cin, int Cmid, int H, int W, int stride);
 
+/* K28h (outside the reference's hot path, like K10): the 1x1 expand and the depthwise 5x5 layer behind it (stride 1 or
+ * 2, zero padding 2 on all four sides) as one launch, with the mean; the Cmid-wide activation between them stays in LDS:
+ *   mid[b, c, p] = rnd16(act1(bias1[c] + sum_k w1[c, k] x[b, k, p]))
+ *   y[b, c, o]   = rnd16(act2(sum_{ky, kx} w_dw[c, ky, kx] mid[b, c, stride o + (ky - 2, kx - 2)] + bias_dw[c]))
+ *   row_mean[b, c] = (1 / (OH OW)) * sum_o f32(y[b, c, o])                                    (where row_mean != NULL)
+ * y [B, Cmid, OH, OW], OH = (H - 1) / stride + 1 and OW = (W - 1) / stride + 1, and row_mean have the BITS of
+ * mtr_conv1x1_bias_act16(x, w1, bias1, NULL, NULL, act1) followed by mtr_depthwise5x5_bias_act_padded(mid, w_dw,
+ * bias_dw, act2, stride, 2, 2, 2, 2, row_mean): the accumulator started at 0, 25 fmaf with ky outer and kx inner, the
+ * bias added last, one rounding, the mean from the rounded outputs in K15's order (units of 4 x 4 or 2 x 4 outputs, lane
+ * l of G adding the unit sums l, l + G, ..., the xor butterfly).
+ * MTR_E_SHAPE (the caller keeps the two-kernel chain) unless: stride 1 or 2; Cin % 8 == 0; H W % 8 == 0; W % 4 == 0;
+ * OW % 4 == 0; H + 4 <= 112 and W + 4 <= 112; B Cmid < 2^30; and the image of a slice of 32 expanded channels, with the
+ * staging buffers or unit sums beside it, fits 160 KiB of LDS (mtr_expand_dw16_k5_lds_bytes: 32x32 at stride 1 and
+ * 28x52 at stride 1 do, 40x40 and 64x64 do not).  w_dw is [Cmid][5][5].  A NULL x, w1, bias1, w_dw, bias_dw or y is
+ * MTR_E_NULL; act1_code / act2_code outside 0..3 are MTR_E_PARAM; y overlapping x is MTR_E_PARAM.  Checked in the order
+ * NULL, dtype, shape, parameters, alignment (x, w1, y 16 bytes), overlap, on the host before anything is enqueued and
+ * without reading a pointer; B == 0 returns MTR_OK without a launch.  No atomics, no split-K, no workspace; only
+ * enqueues on `stream`: the same inputs give the same bits for any batch index, on every call and graph replay. */
+int mtr_expand_dw16_k5(const void* x, int dtype, const void* w1 /*[Cmid][Cin]*/, const float* bias1, int act1_code,
+                       const float* w_dw /*[Cmid][5][5]*/, const float* bias_dw, int act2_code, long long B, int Cin,
+                       int Cmid, int H, int W, int stride, void* y, float* row_mean /* may be NULL */,
+                       mtr_stream_t stream);
+
+/* The same with the workgroup-to-image mapping chosen, as in mtr_expand_dw16_opts.  The bits do not depend on it. */
+int mtr_expand_dw16_k5_opts(const void* x, int dtype, const void* w1, const float* bias1, int act1_code,
+                            const float* w_dw, const float* bias_dw, int act2_code, long long B, int Cin, int Cmid, int H,
+                            int W, int stride, void* y, float* row_mean, mtr_stream_t stream, int mapping);
+
+/* The bytes of LDS one workgroup of mtr_expand_dw16_k5 uses for this shape, or 0 where the entry answers MTR_E_SHAPE
+ * (and for B <= 0).  No GPU work. */
+size_t mtr_expand_dw16_k5_lds_bytes(long long B, int Cin, int Cmid, int H, int W, int stride);
+
 /* K20 (outside the reference's hot path, like K13): mtr_conv1x1_bias_act_pre for f32 tensors, evaluated on the bf16
  * matrix cores from split operands (v_mfma_f32_16x16x32_bf16):
  *   v[b, k, p] = act_in(x[b, k, p] + in_bias[k])  (x itself without in_bias), then v * gate[b, k] with a gate -- f32

@@ -206,6 +206,12 @@ SIGNATURES = {
     'mtr_expand_dw16_tiles': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                       ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mtr_expand_dw16_tiles_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int]),
+    'mtr_expand_dw16_k5': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                   ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mtr_expand_dw16_k5_opts': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                        ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_int]),
+    'mtr_expand_dw16_k5_lds_bytes': (ctypes.c_size_t, [ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int]),
     # a host-only status query WITHOUT a pointer argument: it cannot answer MTR_E_NULL, which the table-driven check of
     # every c_int entry (all pointers NULL, all integers 1) expects.  `int` as restype: ctypes reads the C int and
     # hands it to int(), so the function is declared like the rest and stays outside that check

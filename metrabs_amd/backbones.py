@@ -457,18 +457,22 @@ def _derived_weight(slot, w, make):
     return slot if slot is not None and slot[0] == key else (key, make(w))
 
 
-# The kernels that run the 1x1 expand of an MBConv block and the depthwise 3x3 layer behind it as one launch, in the
-# order an armed expand asks them (their planes are disjoint).  Per kernel, which is also its last_path: the
-# fold_batchnorm option that arms the pairs, the ConvBiasAct field it sets on the expand (a field of its own per option,
-# so no two options arm one field), DepthwiseBiasAct's question, class-wide switch and list of slower shapes, the wrapper
-# in kernels, and whether the call passes the layer's stride (else want_mean).  THE place that says which goes with which.
+# The kernels that run the 1x1 expand of an MBConv block and the depthwise layer behind it (3x3; K28h: 5x5) as one
+# launch, in the order an armed expand asks them (their planes, or their layers, are disjoint).  Per kernel, which is
+# also its last_path: the fold_batchnorm option that arms the pairs, the ConvBiasAct field it sets on the expand (a field
+# of its own per option, so no two options arm one field), DepthwiseBiasAct's question, class-wide switch and list of
+# slower shapes, the wrapper in kernels, and what the call passes beside the tensors: the layer's stride (`strided`; the
+# key of the slower list then carries it as a fifth element) and / or want_mean (`mean`).  THE place that says which goes
+# with which.
 EXPAND_DW_KERNELS = {
     'k25h': dict(option='fuse_expand_depthwise', field='hand_to', takes='k25h_takes', switch='use_k25h',
-                 slower='k25h_slower', fn='expand_depthwise16', strided=False),
+                 slower='k25h_slower', fn='expand_depthwise16', strided=False, mean=True),
     'k26h': dict(option='fuse_expand_depthwise_planes', field='hand_planes_to', takes='k26h_takes',
-                 switch='use_k26h', slower='k26h_slower', fn='expand_depthwise16_planes', strided=False),
+                 switch='use_k26h', slower='k26h_slower', fn='expand_depthwise16_planes', strided=False, mean=True),
     'k27h': dict(option='fuse_expand_depthwise_tiles', field='hand_tiles_to', takes='k27h_takes',
-                 switch='use_k27h', slower='k27h_slower', fn='expand_depthwise16_tiles', strided=True),
+                 switch='use_k27h', slower='k27h_slower', fn='expand_depthwise16_tiles', strided=True, mean=False),
+    'k28h': dict(option='fuse_expand_depthwise5x5', field='hand_k5_to', takes='k28h_takes', switch='use_k28h',
+                 slower='k28h_slower', fn='expand_depthwise16_k5', strided=True, mean=True),
 }
 
 
@@ -486,8 +490,8 @@ class ConvBiasAct(nn.Module):
         self.emit_mean = False  # a squeeze-excite block follows: give it its x.mean((2, 3)) for free
         self._mean = None
         self._gate = None
-        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate', 'k25h' / 'k26h' / 'k27h' (handed over to
-        # the depthwise layer behind) or 'library': what the last forward ran (tests, A/B runs)
+        # 'k13', 'k13_gate', 'k20', 'k20_gate', 'k13h', 'k13h_gate', 'k13h_deep', 'k13h_deep_gate', 'k25h' / 'k26h' / 'k27h' /
+        # 'k28h' (handed over to the depthwise layer behind) or 'library': what the last forward ran (tests, A/B runs)
         self.last_path = None
 
     # class-wide switch (tests and A/B runs): 1x1 convolutions on K13 instead of rocBLAS + K10
@@ -607,10 +611,13 @@ class ConvBiasAct(nn.Module):
     # and by fold_batchnorm(fuse_expand_depthwise_tiles=True): that layer, of stride 1 or 2 and without a mean, runs
     # both as one launch in bands of rows on the large planes the other two refuse (K27h).  Again a field of its own
     hand_tiles_to = ()
+    # and by fold_batchnorm(fuse_expand_depthwise5x5=True): the 5x5 DepthwiseBiasAct of stride 1 or 2 behind this
+    # layer, which runs both as one launch, with its mean (K28h).  A field of its own once more
+    hand_k5_to = ()
 
     def _handed_kernel(self, x, residual=None, pre=None, defer_epilogue=False):
-        """'k25h' / 'k26h' / 'k27h' where forward(x, ...) hands `x` over to the depthwise layer behind, else None.  The
-        three kernels' planes are disjoint."""
+        """'k25h' / 'k26h' / 'k27h' / 'k28h' where forward(x, ...) hands `x` over to the depthwise layer behind, else
+        None.  The three 3x3 kernels' planes are disjoint, and K28h's layers are 5x5."""
         if residual is not None or pre is not None or defer_epilogue:
             return None
         for kernel, cfg in EXPAND_DW_KERNELS.items():
@@ -667,8 +674,8 @@ class ConvBiasAct(nn.Module):
         """defer_epilogue / pre: between the two layers of an armed FusedMBConv (FusedMBConv._forward_pre) only.
         defer_epilogue=True returns self.conv(x) alone; `pre` is the ConvBiasAct whose conv produced `x` that way:
         its "+ bias, activation" is applied here, inside K13 or K20 where one takes `x`, by K10 in front of the library
-        path otherwise.  An armed expand (hand_to, hand_planes_to, hand_tiles_to) whose depthwise layer takes `x` hands
-        it over and returns it untouched: that layer's forward runs both (K25h, K26h, K27h)."""
+        path otherwise.  An armed expand (hand_to, hand_planes_to, hand_tiles_to, hand_k5_to) whose depthwise layer takes
+        `x` hands it over and returns it untouched: that layer's forward runs both (K25h, K26h, K27h, K28h)."""
         handed = self._handed_kernel(x, residual, pre, defer_epilogue)
         if handed is not None:
             # decided here, once: the depthwise layer runs this convolution, its bias and its activation itself
@@ -1051,7 +1058,7 @@ class DepthwiseBiasAct(nn.Module):
         self.act_name = None if act is None else _ACT_NAMES[type(act)]
         self.emit_mean = False
         self._mean = None
-        self.last_path = None  # 'k11', 'k15', 'k18', 'k25h', 'k26h', 'k27h' or 'library': what the last forward ran (tests, A/B runs)
+        self.last_path = None  # 'k11', 'k15', 'k18', 'k25h', 'k26h', 'k27h', 'k28h' or 'library': what the last forward ran (tests, A/B runs)
         # fold_batchnorm(block_depthwise=True) sets this on the k = 3, stride-1, padding-1 layers: they run K18 on
         # the planes it takes and K11's block kernel refuses -- the bits of K11's generic kernel, which those planes
         # run on otherwise
@@ -1087,12 +1094,13 @@ class DepthwiseBiasAct(nn.Module):
                              (112, 672, 16, 16)})
     _handed = None
 
-    def _expand_dw_candidate(self, x, expand, strides, switch):
-        """What k25h_takes, k26h_takes and k27h_takes ask first: the class-wide `switch` is on, this is a 3x3 padding-1
-        layer of a stride in `strides` without a folded ZeroPad2d, an inference call on both weights, a CUDA
-        NCHW-contiguous input of the copy's dtype that `expand` would run on K13h with no gate held."""
+    def _expand_dw_candidate(self, x, expand, strides, switch, k=3, pad=1):
+        """What k25h_takes, k26h_takes, k27h_takes and k28h_takes ask first: the class-wide `switch` is on, this is a
+        `k` x `k` padding-`pad` layer (3 and 1; K28h: 5 and 2) of a stride in `strides` without a folded ZeroPad2d, an
+        inference call on both weights, a CUDA NCHW-contiguous input of the copy's dtype that `expand` would run on
+        K13h with no gate held."""
         c = expand.conv
-        if not (getattr(DepthwiseBiasAct, switch) and self.k == 3 and self.stride in strides and self.pad == 1
+        if not (getattr(DepthwiseBiasAct, switch) and self.k == k and self.stride in strides and self.pad == pad
                 and self.pads is None and x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _16BIT
                 and x.dtype == c.weight.dtype and _inference_call(c.weight, self.weight)):
             return False
@@ -1105,7 +1113,7 @@ class DepthwiseBiasAct(nn.Module):
         call on both weights, a CUDA NCHW-contiguous input of the copy's dtype that the expand would run on K13h with
         no gate held, a plane K11 runs on its block kernel, a shape the C entry accepts and that is not listed as
         slower.  Everything else runs the chain: today's branch, today's bits."""
-        if not self._expand_dw_candidate(x, expand, (1,), 'use_k25h'):
+        if not self._expand_dw_candidate(x, expand, (1,), 'use_k25h', 3, 1):
             return False
         c, (B, K, H, W) = expand.conv, x.shape
         return (kernels.k11_takes_block_kernel(H, W)
@@ -1124,7 +1132,7 @@ class DepthwiseBiasAct(nn.Module):
     def k26h_takes(self, x, expand):
         """k25h_takes for K26h (expand_dw16_planes.hip): the same conditions, but the plane is one K11 does NOT run on
         its block kernel -- 24x24, 12x12 -- and the C entry of K26h accepts the shape."""
-        if not self._expand_dw_candidate(x, expand, (1,), 'use_k26h'):
+        if not self._expand_dw_candidate(x, expand, (1,), 'use_k26h', 3, 1):
             return False
         c, (B, K, H, W) = expand.conv, x.shape
         return (not kernels.k11_takes_block_kernel(H, W)
@@ -1145,7 +1153,7 @@ class DepthwiseBiasAct(nn.Module):
         or 2, and the plane is one of stride 2, or a stride-1 plane that is neither a block-kernel plane (K25h's, or the
         chain's with other bits) nor one K26h's entry accepts -- so the three kernels never compete for a plane -- and
         the C entry of K27h accepts the shape."""
-        if self.emit_mean or not self._expand_dw_candidate(x, expand, (1, 2), 'use_k27h'):
+        if self.emit_mean or not self._expand_dw_candidate(x, expand, (1, 2), 'use_k27h', 3, 1):
             return False
         c, (B, K, H, W) = expand.conv, x.shape
         if self.stride == 1 and (kernels.k11_takes_block_kernel(H, W)
@@ -1154,15 +1162,35 @@ class DepthwiseBiasAct(nn.Module):
         return ((K, c.out_channels, H, W, self.stride) not in DepthwiseBiasAct.k27h_slower
                 and kernels.expand_depthwise16_tiles_supported(x, c.weight, self.stride))
 
+    # K28h (fold_batchnorm(fuse_expand_depthwise5x5=True)): the class-wide switch, and the (Cin, Cmid, H, W, stride) of
+    # the expand's input where K28h was not ahead of the chain K13h + K15 in every round of tools/expand_dw_ab.py
+    # --kernel k28h: EVERY class timed so far (MobileNetV3 batch 320 at 256 px, f16 and bf16, the same three in both,
+    # 0.52 - 0.61x; DESIGN.md section 36, profiles/r26a_expand_dw_ab_k28h.jsonl).  As shipped the armed pairs of that
+    # network therefore keep the chain at 256 px; other resolutions, batch sizes and networks have not been timed
+    use_k28h = True
+    k28h_slower = frozenset({(40, 120, 32, 32, 1), (112, 672, 16, 16, 2), (160, 960, 8, 8, 1)})
+
+    def k28h_takes(self, x, expand):
+        """k25h_takes for K28h (expand_dw16_k5.hip): this is a 5x5 padding-2 layer of stride 1 or 2 without a folded
+        ZeroPad2d, with or without a mean, that would run K15 on the expanded tensor (what path() says of it); the
+        shape is not listed as slower and the C entry of K28h accepts it."""
+        if not self._expand_dw_candidate(x, expand, (1, 2), 'use_k28h', 5, 2):
+            return False
+        c, (B, K, H, W) = expand.conv, x.shape
+        return ((c.out_channels, H, W, self.stride) not in DepthwiseBiasAct.k15_slower
+                and kernels.depthwise5x5_supported(H, W, self.pad)
+                and (K, c.out_channels, H, W, self.stride) not in DepthwiseBiasAct.k28h_slower
+                and kernels.expand_depthwise16_k5_supported(x, c.weight, self.stride))
+
     def hand_over(self, x, expand, kernel='k25h'):
         """From the armed expand in front: `x` comes WITHOUT that convolution applied; the next forward(x) runs it, on
-        `kernel` ('k25h' / 'k26h' / 'k27h') where this layer still takes it."""
+        `kernel` ('k25h' / 'k26h' / 'k27h' / 'k28h') where this layer still takes it."""
         self._handed = (x, expand, kernel)
 
     def path(self, x):
         """Which path forward(x) runs on an input that was not handed over, as last_path will say it: 'k18' (an armed
-        3x3 layer), then 'k11' (3x3) or 'k15' (5x5), then 'library' (the torch ops).  ('k25h' / 'k26h' / 'k27h': forward, on
-        the input an armed expand handed over.)"""
+        3x3 layer), then 'k11' (3x3) or 'k15' (5x5), then 'library' (the torch ops).  ('k25h' / 'k26h' / 'k27h' / 'k28h':
+        forward, on the input an armed expand handed over.)"""
         pl, pr = (self.pad, self.pad) if self.pads is None else self.pads[:2]
         ow = (x.shape[3] + pl + pr - self.k) // self.stride + 1
         if not (x.is_cuda and x.is_contiguous() and ow % 4 == 0 and x.dtype in _FLOATS):
@@ -1181,16 +1209,19 @@ class DepthwiseBiasAct(nn.Module):
             cfg = EXPAND_DW_KERNELS[kernel]
             if getattr(self, cfg['takes'])(x, expand):
                 self.last_path = kernel
-                # (a strided kernel's layer emits no mean; the stride is an argument)
-                extra = dict(stride=self.stride) if cfg['strided'] else dict(want_mean=self.emit_mean)
+                # (what the row says: the stride as an argument, the mean where the kernel has one -- a layer of a
+                # kernel without a mean emits none)
+                extra = dict(stride=self.stride) if cfg['strided'] else {}
+                if cfg['mean']:
+                    extra['want_mean'] = self.emit_mean
                 out = getattr(kernels, cfg['fn'])(x, expand.conv.weight, expand.bias, expand.act_name, self.weight,
                                                   self.bias, self.act_name, **extra)
                 if not self.emit_mean:
                     return out
                 self._mean = out
                 return out[0]
-            # (the expand asked k25h_takes / k26h_takes / k27h_takes before it handed x over; whatever changed since: never
-            # un-expanded)
+            # (the expand asked k25h_takes / k26h_takes / k27h_takes / k28h_takes before it handed x over; whatever
+            # changed since: never un-expanded)
             x = expand.forward_here(x)
         path = self.last_path = self.path(x)
         if path != 'library':
@@ -1417,7 +1448,7 @@ def _arm_deep_projects(folded):
             m.deep_projects = True
 
 
-def _arm_expand_depthwise(folded, field='hand_to', strides=(1,)):
+def _arm_expand_depthwise(folded, field='hand_to', strides=(1,), k=3):
     """fuse_expand_depthwise: every plain 1x1 ConvBiasAct that emits no mean and stands directly in front of a 3x3,
     stride-1, padding-1 DepthwiseBiasAct of as many channels without a folded ZeroPad2d -- the expand and depthwise
     layers of the stride-1 MBConv blocks: 28 pairs of EfficientNetV2-S, 59 of -L, 6 of MobileNetV3, none of ResNet-18
@@ -1431,12 +1462,15 @@ def _arm_expand_depthwise(folded, field='hand_to', strides=(1,)):
     depthwise layer has padding 1, no folded ZeroPad2d and no squeeze-excite block behind it (K27h has no mean), directly
     behind the expand -- 6 + 2 pairs of MobileNetV3; the stride-2 layers of EfficientNetV2 carry a folded padding or, the
     one symmetric one of each network, emit the mean, and stay unarmed (28 of -S, 59 of -L) -- for K27h ('k27h';
-    DepthwiseBiasAct.k27h_takes: the large planes of the layers without a squeeze-excite mean)."""
+    DepthwiseBiasAct.k27h_takes: the large planes of the layers without a squeeze-excite mean).
+    fuse_expand_depthwise5x5 arms on 'hand_k5_to', with `k` 5 and `strides` (1, 2), the pairs whose depthwise layer is
+    5x5 with padding 2 (k // 2) and no folded ZeroPad2d, a mean behind it allowed at either stride: 6 pairs of
+    MobileNetV3, none of the other three networks -- for K28h ('k28h'; DepthwiseBiasAct.k28h_takes)."""
     for _, _, a, b in _adjacent_children(folded):
         expand, dw = _only_layer(a), _only_layer(b)
         if type(expand) is ConvBiasAct and not expand.emit_mean and _plain_1x1(expand.conv) \
-                and isinstance(dw, DepthwiseBiasAct) and dw.k == 3 and dw.stride in strides and dw.pad == 1 \
-                and (dw.stride == 1 or not dw.emit_mean) \
+                and isinstance(dw, DepthwiseBiasAct) and dw.k == k and dw.stride in strides and dw.pad == k // 2 \
+                and (k == 5 or dw.stride == 1 or not dw.emit_mean) \
                 and dw.pads is None and dw.weight.shape[0] == expand.conv.out_channels:
             setattr(expand, field, (dw,))
 
@@ -1472,13 +1506,14 @@ _NEEDS = {'fused': (lambda fused, dtype: fused, 'fused_epilogue=True'),
 _OPTION_NEEDS = (('fuse_blocks', '16bit'), ('fuse_stem', 'fused'), ('block_depthwise', 'fused'),
                  ('deep_projects', '16bit'), ('winograd3x3', 'f32'), ('split_gemm', 'f32'),
                  ('strided3x3', 'f32'), ('split3x3', 'f32'), ('fuse_expand_depthwise', '16bit'),
-                 ('fuse_expand_depthwise_planes', '16bit'), ('fuse_expand_depthwise_tiles', '16bit'))
+                 ('fuse_expand_depthwise_planes', '16bit'), ('fuse_expand_depthwise_tiles', '16bit'),
+                 ('fuse_expand_depthwise5x5', '16bit'))
 
 
 def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                    block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
                    strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False,
-                   fuse_expand_depthwise_tiles=False, split3x3=False):
+                   fuse_expand_depthwise_tiles=False, split3x3=False, fuse_expand_depthwise5x5=False):
     """Inference-time copy of `backbone` with every batch norm folded into the convolution in front
     of it (w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps)): the same
     function up to rounding (features equal to ~1e-5 relative in f32), one elementwise pass over
@@ -1514,8 +1549,11 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     fuse_expand_depthwise_tiles=True (needs a 16-bit dtype): the same pairs and the stride-2 pairs without a folded
     padding as one launch on the large planes of the layers that emit no mean (64x64, 128x128 -> 64x64, 32x32 -> 16x16 of
     MobileNetV3), K27h (_arm_expand_depthwise on hand_tiles_to).
+    fuse_expand_depthwise5x5=True (needs a 16-bit dtype): the 1x1 expand and the depthwise 5x5 layer of stride 1 or 2 of an
+    MBConv block as one launch, with the squeeze-excite mean, K28h (_arm_expand_depthwise on hand_k5_to with k = 5: the six
+    5x5 blocks of MobileNetV3).
     The options of one family combine freely (f32: fuse_stem, block_depthwise, winograd3x3, split_gemm, strided3x3, split3x3; 16-bit:
-    fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise, fuse_expand_depthwise_planes, fuse_expand_depthwise_tiles): no two of them arm the same field of the same module, and
+    fuse_blocks, fuse_stem, block_depthwise, deep_projects, fuse_expand_depthwise, fuse_expand_depthwise_planes, fuse_expand_depthwise_tiles, fuse_expand_depthwise5x5): no two of them arm the same field of the same module, and
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
     module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
@@ -1534,7 +1572,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
                    deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
                    strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise,
                    fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
-                   fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3)
+                   fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3,
+                   fuse_expand_depthwise5x5=fuse_expand_depthwise5x5)
     for option, need in _OPTION_NEEDS:
         met, text = _NEEDS[need]
         if options[option] and not met(fused_epilogue, dtype):
@@ -1568,6 +1607,8 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
         _arm_expand_depthwise(folded, 'hand_planes_to')
     if fuse_expand_depthwise_tiles:
         _arm_expand_depthwise(folded, 'hand_tiles_to', strides=(1, 2))
+    if fuse_expand_depthwise5x5:
+        _arm_expand_depthwise(folded, 'hand_k5_to', strides=(1, 2), k=5)
     if fuse_stem:
         _fuse_stem(folded)
     return folded

@@ -24,8 +24,11 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-
 # depthwise5x5.hip: the SLP vectoriser pairs the 400 fma of a 4x4 output block into v_pk_fma_f32 and then needs 195
 # (f32) to 267 (16-bit) VGPRs for the shuffled operands -- one or two waves per SIMD, and spills when bounded to
 # four; without it the kernels take 113 - 118 VGPRs and no scratch.
+# expand_dw16_k5.hip: the same fma block behind an MFMA phase; 200 - 202 VGPRs at stride 1 with the vectoriser,
+# 160 - 164 without; with its 64 AGPRs the 64-channel configuration keeps two waves per SIMD only without.
 EXTRA_FLAGS = {'head_rt.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
-               'depthwise5x5.hip': ['-fno-slp-vectorize']}
+               'depthwise5x5.hip': ['-fno-slp-vectorize'],
+               'expand_dw16_k5.hip': ['-fno-slp-vectorize']}
 
 
 def sources():

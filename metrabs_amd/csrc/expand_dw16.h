@@ -23,6 +23,9 @@
 //            first, so phase 2 needs no bounds test.
 //   phase 2  each kernel's own (K11's block arithmetic, K11's generic walk with the mean, K27h's segments): in its file.
 //
+// K28h (expand_dw16_k5.hip) builds the same pair for the depthwise 5x5 layers (K15's arithmetic and mean, stride 1 or 2)
+// from the same pieces: phase 1 as edw_gemm_span in passes over the plane, the image beside the staging buffers.
+//
 // No atomics, no split-K, no workspace: the same inputs give the same bits.
 #pragma once
 #include "common.h"
@@ -157,13 +160,14 @@ __device__ __forceinline__ void edw_mfma_ktile(edw_f32x16 (&acc)[FM][FN], const 
   }
 }
 
-// conv1x1_16_kernel's loop over the whole plane of one image, positions 0 .. HW - 1 behind xb (past HW: zero-filled),
-// through two buffers xs[2][BN * kEdwLDK]: the next k-tile's loads are in flight during this one's MFMAs.  Ends on a
-// barrier: the buffers are free.  (K27h, one buffer of a run-time ldk, runs its own loop of the same pieces.)
-template <class Hh, int BN, int FM, int FN>
-__device__ __forceinline__ void edw_gemm_plane(edw_f32x16 (&acc)[FM][FN], unsigned short* xs, const unsigned short* xb,
-                                               const unsigned short* w1, int mrow, int M, int K, int HW, int tid,
-                                               EdwPlaneTiles tiles) {
+// conv1x1_16_kernel's loop over a span of one image's plane, positions 0 .. n_pos - 1 behind xb (past n_pos:
+// zero-filled; HW: the plane, a channel's stride), through two buffers xs[2][BN * kEdwLDK]: the next k-tile's loads are
+// in flight during this one's MFMAs.  Ends on a barrier: the buffers are free.  (K27h, one buffer of a run-time ldk,
+// runs its own loop of the same pieces.)
+template <class Hh, int BN, int FM, int FN, class Tiles>
+__device__ __forceinline__ void edw_gemm_span(edw_f32x16 (&acc)[FM][FN], unsigned short* xs, const unsigned short* xb,
+                                              const unsigned short* w1, int mrow, int M, int K, int HW, int n_pos,
+                                              int tid, Tiles tiles) {
   constexpr int BK = kEdwBK, LDK = kEdwLDK, KS = kEdwKS;
   const int r = tid & 31, h = (tid & 63) >> 5;
   const auto all = [](int, int) { return true; };
@@ -171,14 +175,14 @@ __device__ __forceinline__ void edw_gemm_plane(edw_f32x16 (&acc)[FM][FN], unsign
   edw_clear(acc);
   uint4 wc[FM][KS], wnx[FM][KS];
   const int n_tiles = (K + BK - 1) / BK;
-  xt.load(xb, tid, 0, K, HW, HW);
+  xt.load(xb, tid, 0, K, HW, n_pos);
   edw_load_w(wc, w1, mrow, M, K, 0, h);
   xt.store(xs, LDK, tid, all);
   __syncthreads();
   for (int t = 0; t < n_tiles; ++t) {
     const int buf = t & 1;
     if (t + 1 < n_tiles) {  // in flight during this tile's MFMAs
-      xt.load(xb, tid, (t + 1) * BK, K, HW, HW);
+      xt.load(xb, tid, (t + 1) * BK, K, HW, n_pos);
       edw_load_w(wnx, w1, mrow, M, K, (t + 1) * BK, h);
     }
     edw_mfma_ktile<Hh>(acc, wc, &xs[buf * (BN * LDK) + r * LDK + 8 * h], LDK, tiles);
@@ -191,6 +195,14 @@ __device__ __forceinline__ void edw_gemm_plane(edw_f32x16 (&acc)[FM][FN], unsign
     }
     __syncthreads();
   }
+}
+
+// the same over the whole plane of one image (K25h, K26h)
+template <class Hh, int BN, int FM, int FN>
+__device__ __forceinline__ void edw_gemm_plane(edw_f32x16 (&acc)[FM][FN], unsigned short* xs, const unsigned short* xb,
+                                               const unsigned short* w1, int mrow, int M, int K, int HW, int tid,
+                                               EdwPlaneTiles tiles) {
+  edw_gemm_span<Hh, BN>(acc, xs, xb, w1, mrow, M, K, HW, HW, tid, tiles);
 }
 
 // ---- between the phases

@@ -1029,10 +1029,10 @@ def _expand_dw16_supported(x, w1, query, *extra):
     return getattr(_lib.load(), query)(B, K, w1.shape[0], H, W, *extra) > 0
 
 
-def _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, stride=1):
+def _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, stride=1, k=3):
     """The argument checks of the wrapper `name`, in their order -> (B, Cin, Cmid, H, W, w1 as [Cmid, Cin]).  `stride`
-    is expand_depthwise16_tiles' alone (the other two have none and leave the default): its refusal keeps its place,
-    right behind x's."""
+    is expand_depthwise16_tiles' and expand_depthwise16_k5's (the other two have none and leave the default): its
+    refusal keeps its place, right behind x's.  `k`: the depthwise kernel size, 3 or expand_depthwise16_k5's 5."""
     if x.dim() != 4 or not x.is_contiguous():
         raise ValueError(f'{name}: x must be [B, Cin, H, W], NCHW-contiguous')
     if stride not in (1, 2):
@@ -1044,8 +1044,8 @@ def _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, stride=1):
         raise ValueError(f'{name}: the 1x1 weight has {w1.shape[1]} input channels, x has {K}')
     if w1.dtype != x.dtype:
         raise ValueError(f'{name}: the 1x1 weight is {w1.dtype}, x is {x.dtype}')
-    if w_dw.numel() != Cmid * 9:
-        raise ValueError(f'{name}: the depthwise weight must be [{Cmid}, 3, 3], got {tuple(w_dw.shape)}')
+    if w_dw.numel() != Cmid * k * k:
+        raise ValueError(f'{name}: the depthwise weight must be [{Cmid}, {k}, {k}], got {tuple(w_dw.shape)}')
     if bias1.numel() != Cmid or bias_dw.numel() != Cmid:
         raise ValueError(f'{name}: biases have {bias1.numel()} and {bias_dw.numel()} elements, expected {Cmid} each')
     return B, K, Cmid, H, W, w1
@@ -1145,6 +1145,42 @@ def expand_depthwise16_tiles(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, 
         _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
         int(stride), _ptr(out), current_stream_ptr(x.device)), 'mtr_expand_dw16_tiles')
     return out
+
+
+# K28h: the 1x1 expand and the depthwise 5x5 layer behind it (K15), stride 1 or 2, padding 2, with the mean
+# (csrc/expand_dw16_k5.hip)
+
+def expand_depthwise16_k5_supported(x, w1, stride=1):
+    """Whether mtr_expand_dw16_k5 takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous, both
+    16-byte aligned, Cin a multiple of 8, stride 1 or 2, W % 4 == 0, H W % 8 == 0, an output row of a multiple of four
+    elements, a padded plane of at most 112 x 112 (K15's bound), fewer than 2^30 planes of output, and the image of 32
+    expanded channels inside 160 KiB of LDS -- 32x32 at stride 1 is, 64x64 is not (its MTR_E_DTYPE / MTR_E_SHAPE /
+    MTR_E_ALIGN rules, checked without a launch).  `w1` is the expand's weight, [Cmid, Cin] or [Cmid, Cin, 1, 1]."""
+    return _expand_dw16_supported(x, w1, 'mtr_expand_dw16_k5_lds_bytes', int(stride))
+
+
+def expand_depthwise16_k5(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, want_mean=False, out=None,
+                          mapping='auto'):
+    """K28h: y = act2(depthwise_conv5x5(act1(conv1x1(x, w1) + bias1), w_dw, stride, padding 2) + bias_dw) in one launch
+    on the current stream (+ the [B, Cmid] f32 mean of y over its plane if want_mean), the expanded activation kept in
+    LDS; w_dw [Cmid, 1, 5, 5] or [Cmid, 5, 5].  y [B, Cmid, (H - 1) // stride + 1, (W - 1) // stride + 1] and the mean
+    have the bits of conv1x1_bias_act16 followed by depthwise5x5_bias_act(.., stride, 2, want_mean=True), the same on
+    every call and graph replay, and for every `mapping` (a key of EXPAND_DW16_MAPPINGS).  What the kernel does not take
+    raises (expand_depthwise16_k5_supported asks first); there is no fallback in here."""
+    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
+    code = EXPAND_DW16_MAPPINGS[mapping]
+    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_k5', x, w1, bias1, w_dw, bias_dw, stride, k=5)
+    out = _residual_and_out('expand_depthwise16_k5', x, (B, Cmid, (H - 1) // stride + 1, (W - 1) // stride + 1), None,
+                            out)
+    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
+    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
+            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
+            int(stride), _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
+    if code < 0:
+        check(_lib.load().mtr_expand_dw16_k5(*args), 'mtr_expand_dw16_k5')
+    else:
+        check(_lib.load().mtr_expand_dw16_k5_opts(*args, code), 'mtr_expand_dw16_k5_opts')
+    return (out, mean) if want_mean else out
 
 
 # K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one

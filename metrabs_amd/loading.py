@@ -57,7 +57,8 @@ def load_joint_info(model_dir):
 def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_epilogue=False, dtype=None,
                     fuse_blocks=False, fuse_stem=False, block_depthwise=False, deep_projects=False,
                     winograd3x3=False, split_gemm=False, strided3x3=False, fuse_expand_depthwise=False,
-                    fuse_expand_depthwise_planes=False, fuse_expand_depthwise_tiles=False, split3x3=False):
+                    fuse_expand_depthwise_planes=False, fuse_expand_depthwise_tiles=False, split3x3=False,
+                    fuse_expand_depthwise5x5=False):
     """demo_image.py:59-74 -> Metrabs in eval mode with the checkpoint loaded (strict).
     fold_batchnorm=True then replaces the backbone by its inference copy with every batch norm
     folded into the convolution in front of it (backbones.fold_batchnorm: the same function up to
@@ -101,7 +102,10 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
     (backbones.fold_batchnorm(fuse_expand_depthwise_planes=True), K26h): the same bits.
     fuse_expand_depthwise_tiles=True (a 16-bit dtype only, else ValueError; off by default) does the same, in bands of
     rows, on the large planes of the stride-1 and stride-2 pairs that feed no squeeze-excite block
-    (backbones.fold_batchnorm(fuse_expand_depthwise_tiles=True), K27h): the same bits."""
+    (backbones.fold_batchnorm(fuse_expand_depthwise_tiles=True), K27h): the same bits.
+    fuse_expand_depthwise5x5=True (a 16-bit dtype only, else ValueError; off by default) runs the 1x1 expand and the
+    depthwise 5x5 layer (stride 1 or 2, with its squeeze-excite mean) of the copy's MBConv blocks as one launch each
+    (backbones.fold_batchnorm(fuse_expand_depthwise5x5=True), K28h): the same bits."""
     if dtype == torch.float32:
         dtype = None
     if dtype not in (None, torch.float16, torch.bfloat16):
@@ -118,6 +122,9 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
                          'torch.bfloat16')
     if fuse_expand_depthwise_tiles and dtype is None:
         raise ValueError('load_crop_model: fuse_expand_depthwise_tiles=True needs dtype=torch.float16 or '
+                         'torch.bfloat16')
+    if fuse_expand_depthwise5x5 and dtype is None:
+        raise ValueError('load_crop_model: fuse_expand_depthwise5x5=True needs dtype=torch.float16 or '
                          'torch.bfloat16')
     if winograd3x3 and dtype is not None:
         raise ValueError('load_crop_model: winograd3x3=True needs an f32 copy (dtype=None or torch.float32)')
@@ -148,7 +155,8 @@ def load_crop_model(model_dir, map_location='cpu', fold_batchnorm=False, fused_e
                               fuse_stem=fuse_stem, block_depthwise=block_depthwise, deep_projects=deep_projects,
                               fuse_expand_depthwise=fuse_expand_depthwise,
                               fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
-                              fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles)
+                              fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles,
+                              fuse_expand_depthwise5x5=fuse_expand_depthwise5x5)
     elif fuse_stem or block_depthwise or winograd3x3 or split_gemm or strided3x3 or split3x3:
         from .backbones import fold_batchnorm as fold
         model.backbone = fold(model.backbone, fused_epilogue=True, fuse_stem=fuse_stem,
@@ -164,17 +172,18 @@ def load_multiperson_model(model_dir, device='cuda', detector=None, fold_batchno
                            fused_epilogue=False, dtype=None, fuse_blocks=False, fuse_stem=False,
                            block_depthwise=False, deep_projects=False, winograd3x3=False, split_gemm=False,
                            strided3x3=False, fuse_expand_depthwise=False, fuse_expand_depthwise_planes=False,
-                           fuse_expand_depthwise_tiles=False, split3x3=False):
+                           fuse_expand_depthwise_tiles=False, split3x3=False, fuse_expand_depthwise5x5=False):
     """demo_image.py:49-56 -> Pose3dEstimator on `device`.  dtype, fuse_blocks, fuse_stem, block_depthwise, deep_projects,
     winograd3x3, split_gemm, strided3x3, split3x3, fuse_expand_depthwise, fuse_expand_depthwise_planes,
-    fuse_expand_depthwise_tiles:
+    fuse_expand_depthwise_tiles, fuse_expand_depthwise5x5:
     as load_crop_model (a 16-bit copy also makes the estimator sample 16-bit crops)."""
     model = load_crop_model(model_dir, fold_batchnorm=fold_batchnorm, fused_epilogue=fused_epilogue, dtype=dtype,
                             fuse_blocks=fuse_blocks, fuse_stem=fuse_stem, block_depthwise=block_depthwise,
                             deep_projects=deep_projects, winograd3x3=winograd3x3, split_gemm=split_gemm,
                             strided3x3=strided3x3, fuse_expand_depthwise=fuse_expand_depthwise,
                             fuse_expand_depthwise_planes=fuse_expand_depthwise_planes,
-                            fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3)
+                            fuse_expand_depthwise_tiles=fuse_expand_depthwise_tiles, split3x3=split3x3,
+                            fuse_expand_depthwise5x5=fuse_expand_depthwise5x5)
     with open(os.path.join(model_dir, 'skeleton_infos.pkl'), 'rb') as f:
         skeleton_infos = pickle.load(f)
     joint_transform_matrix = np.load(os.path.join(model_dir, 'joint_transform_matrix.npy'))

@@ -45,6 +45,8 @@ by rounding; the rows carry ab='k21', the paths of the armed layers and the MPJP
 --ab k27h: both arms are the 16-bit copy of the same network (--config 3, MobileNetV3), A folded as by default, B with
 fuse_expand_depthwise_tiles=True (the expand + depthwise 3x3 pairs on large planes as one launch, K27h, where
 DepthwiseBiasAct.k27h_slower does not list them).  The rows carry ab='k27h' and the paths of the armed expands.
+--ab k28h: the same with fuse_expand_depthwise5x5=True (the expand + depthwise 5x5 pairs as one launch, K28h, where
+DepthwiseBiasAct.k28h_slower does not list them).  The rows carry ab='k28h' and the paths of the armed expands.
 
     python tools/backbone16_ab.py --config 1 --out OUT.jsonl      # on the GPU
 """
@@ -65,7 +67,7 @@ def main():
     ap.add_argument('--dtype', choices=['f16', 'bf16', 'f32'], default='f16')
     ap.add_argument('--graph-batches', choices=['auto', 'off'], default='auto')
     ap.add_argument('--ab', choices=['copy', 'k14h', 'k15', 'k16h', 'k17', 'k18', 'deepk', 'k19', 'k20', 'k21', 'k22',
-                                     'k25h', 'k26h', 'k27h'],
+                                     'k25h', 'k26h', 'k27h', 'k28h'],
                     default='copy',
                     help="copy: autocast vs the 16-bit copy; k14h: the copy with K14h off vs on; k15: the copy (f32 with "
                          "--dtype f32) folded without vs with K15; k16h: the copy folded without vs with fuse_blocks; k17: without vs with fuse_stem; "
@@ -77,7 +79,8 @@ def main():
                          "k25h: the 16-bit copy folded without vs with fuse_expand_depthwise; "
                          "k26h: the 16-bit copy folded without vs with fuse_expand_depthwise_planes (--config 4, or "
                          "--config 1 --res 384); "
-                         "k27h: the 16-bit copy folded without vs with fuse_expand_depthwise_tiles (--config 3)")
+                         "k27h: the 16-bit copy folded without vs with fuse_expand_depthwise_tiles (--config 3); "
+                         "k28h: the 16-bit copy folded without vs with fuse_expand_depthwise5x5 (--config 3)")
     ap.add_argument('--res', type=int, default=None, help='crop side handed to bench.py (its --res) instead of the '
                                                           "config's own")
     ap.add_argument('--winograd3x3', action='store_true',
@@ -85,9 +88,9 @@ def main():
     ap.add_argument('--out', required=True)
     args = ap.parse_args()
     if (args.dtype == 'f32' or args.config == 3) and args.ab not in ('k15', 'k17', 'k18', 'k19', 'k20', 'k21', 'k22') \
-            and not (args.ab == 'k27h' and args.dtype != 'f32'):
+            and not (args.ab in ('k27h', 'k28h') and args.dtype != 'f32'):
         ap.error('--dtype f32 and --config 3 go with --ab k15, --ab k17, --ab k18, --ab k19, --ab k20, --ab k21 or --ab k22 '
-                 '(--config 3 with a 16-bit dtype also with --ab k27h)')
+                 '(--config 3 with a 16-bit dtype also with --ab k27h and --ab k28h)')
     if args.ab in ('k19', 'k20', 'k21', 'k22') and args.dtype != 'f32':
         ap.error(f'--ab {args.ab} goes with --dtype f32')
     if args.winograd3x3 and args.ab not in ('k20', 'k21', 'k22'):
@@ -195,6 +198,12 @@ def main():
         est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
                                                    fuse_expand_depthwise_tiles=True)
         assert any(isinstance(m, ConvBiasAct) and m.hand_tiles_to for m in est_b.crop_model.backbone.modules())
+    if args.ab == 'k28h':                                        # the same, armed for MobileNetV3's 5x5 pairs
+        est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
+        est_a.crop_dtype = est_a.crop_model.input_dtype
+        est_b.crop_model.backbone = fold_batchnorm(est_b.reference_backbone, fused_epilogue=True, dtype=dt,
+                                                   fuse_expand_depthwise5x5=True)
+        assert any(isinstance(m, ConvBiasAct) and m.hand_k5_to for m in est_b.crop_model.backbone.modules())
     if args.ab == 'k14h':                                        # arm A: the same copy, K14h switched off
         est_a.crop_model.backbone = fold_batchnorm(est_a.reference_backbone, fused_epilogue=True, dtype=dt)
         est_a.crop_dtype = est_a.crop_model.input_dtype
@@ -285,6 +294,14 @@ def main():
         paths = [m.last_path for m in est_b.crop_model.backbone.modules()
                  if isinstance(m, ConvBiasAct) and m.hand_tiles_to]
         row = dict(kind='paths', ab='k27h', res=bargs.res, backbone=bargs.backbone, batch=bargs.batch,
+                   equal_poses=bool(torch.equal(p_a, p_b)),
+                   b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.ab == 'k28h':
+        paths = [m.last_path for m in est_b.crop_model.backbone.modules()
+                 if isinstance(m, ConvBiasAct) and m.hand_k5_to]
+        row = dict(kind='paths', ab='k28h', res=bargs.res, backbone=bargs.backbone, batch=bargs.batch,
                    equal_poses=bool(torch.equal(p_a, p_b)),
                    b={str(k): paths.count(k) for k in sorted(set(paths), key=str)})
         print(json.dumps(row), flush=True)

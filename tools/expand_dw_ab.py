@@ -30,6 +30,13 @@ MobileNetV3 at batch 320 and 256 px it takes: 24 -> 72 on 64x64 at stride 1 (wit
 40 -> 240 on 32x32 at stride 2.  A key carries the stride as a fifth element, as DepthwiseBiasAct.k27h_slower does; the
 byte floor counts x and W1 read once and the (stride-2: four times smaller) y written once.  K27h has one
 workgroup-to-image mapping: no 'plain' / 'xcd' arms.
+
+    python tools/expand_dw_ab.py --kernel k28h --out OUT.jsonl
+
+is fold_batchnorm(fuse_expand_depthwise5x5=True), K28h (kernels.expand_depthwise16_k5), on the 5x5 pairs of MobileNetV3
+at batch 320 and 256 px: the chain is K13h + K15 with the squeeze-excite mean.  The key carries the stride, as
+DepthwiseBiasAct.k28h_slower does; the 24 -> 72 pair on 64x64 at stride 2 is outside K28h's LDS rule and is recorded with
+the chain's time alone.  The 'plain' / 'xcd' arms pass the stride and the mean.
 """
 import argparse
 import json
@@ -44,6 +51,7 @@ KERNELS = {
     'k25h': dict(lds='mtr_expand_dw16_lds_bytes', workloads=[('effnetv2-s', 64, 256), ('mobilenetv3', 320, 256)]),
     'k26h': dict(lds='mtr_expand_dw16_planes_lds_bytes', workloads=[('effnetv2-l', 32, 384), ('effnetv2-s', 64, 384)]),
     'k27h': dict(lds='mtr_expand_dw16_tiles_lds_bytes', workloads=[('mobilenetv3', 320, 256)]),
+    'k28h': dict(lds='mtr_expand_dw16_k5_lds_bytes', workloads=[('mobilenetv3', 320, 256)]),
 }
 
 
@@ -136,8 +144,10 @@ def main():
                     return d(e(x))
 
                 def mapped(mapping):
+                    extra = dict(stride=stride) if cfg['strided'] else {}
                     return lambda: getattr(kernels, cfg['fn'])(x, e.conv.weight, e.bias, e.act_name, d.weight, d.bias,
-                                                               d.act_name, want_mean=d.emit_mean, mapping=mapping)
+                                                               d.act_name, want_mean=d.emit_mean, mapping=mapping,
+                                                               **extra)
 
                 def k18():
                     return kernels.depthwise3x3_blocks_bias_act(e.forward_here(x), d.weight, d.bias, d.act_name,
@@ -171,7 +181,7 @@ def main():
                         for n, gr in graphs.items():
                             t[n].append(timed(gr))
                     del graphs
-                byts = 2 * (B * H * W * Cin + B * (H // stride) * (W // stride) * Cmid + Cmid * Cin)
+                byts = 2 * (B * H * W * Cin + B * (-(-H // stride)) * (-(-W // stride)) * Cmid + Cmid * Cin)
                 mid_mb = 2 * B * H * W * Cmid / 1e6
                 floor = byts / (HBM_TBS * 1e12) * 1e6
                 row = dict(backbone=backbone, batch=B, res=res, dtype=dname, cin=Cin, cmid=Cmid, hw=f'{H}x{W}',
