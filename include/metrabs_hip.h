@@ -436,6 +436,16 @@ int mtr_detector_scale_boxes(const float* xyxy_conf, int n, const mtr_detector_g
  *   edges [n_bones,2] + mean_bones [n_bones] of the first J_model joints (n_bones = 0: no bone test).
  *   -> valid [P] (u8, the three plausibility tests), keep_idx [P] (per image: the kept poses as
  *      global row indices, then -1), keep_count [n_images].
+ * A table row that names a joint >= J_model is skipped.  The shape and parameter rules (A, J >= 1,
+ * 1 <= J_model <= J, max_per_image <= 1024, 16 * (J rounded up to even) + 32 * A <= 48 KiB of dynamic
+ * LDS) are checked before anything else, also for n_images = 0.
+ * The workspace is a contract (tests/test_gpu_filter_fuzz.py reads it): first the mean-over-
+ * augmentation poses [P,J,3] float32 (the float32 sum over A in order, divided by A), then, at
+ * sim_offsets[i] floats behind them, image i's similarity matrix: nv_i x nv_i float32, COMPACT, over
+ * the image's valid poses in index order (nv_i <= n_i; symmetric; NaN where J / 4 = 0).  The floats
+ * of an image's n_i^2 behind its nv_i^2 are not written.  mtr_filter_poses_workspace_bytes sizes the
+ * workspace for n_i^2 floats per image: (P * J * 3 + P * max_per_image) * 4 bytes, which holds
+ * sum n_i^2 <= P * max_per_image.
  */
 typedef struct mtr_filter_params {
   float rel_small, rel_big, abs_diff_mm; /* 0.1, 3, 300   plausibility_check.py:22-24            */

@@ -279,12 +279,15 @@ extern "C" int mtr_filter_poses(const float* poses3d, const float* poses2d, cons
                                 size_t workspace_bytes, int max_per_image, uint8_t* valid,
                                 int32_t* keep_idx, int32_t* keep_count, mtr_stream_t stream) {
   if (n_images < 0 || P < 0 || A <= 0 || J <= 0 || n_bones < 0) return MTR_E_SHAPE;
+  // the shape and parameter rules hold for a call without images too (a caller can probe them with n_images = 0)
+  if (max_per_image > 1024) return MTR_E_SHAPE;  // poses per image held in LDS tables
+  if (J_model <= 0 || J_model > J) return MTR_E_PARAM;
+  const size_t lds = (size_t)4 * ((J + 1) & ~1) * sizeof(float) + (size_t)4 * A * sizeof(double);
+  if (lds > 48 * 1024) return MTR_E_SHAPE;
   if (n_images == 0) return MTR_OK;
   if (!row_start || !sim_offsets || !keep_count || !fp) return MTR_E_NULL;
   if (P > 0 && (!poses3d || !poses2d || !boxes || !workspace || !valid || !keep_idx)) return MTR_E_NULL;
   if (n_bones > 0 && (!edges || !mean_bones)) return MTR_E_NULL;
-  if (max_per_image > 1024) return MTR_E_SHAPE;  // poses per image held in LDS tables
-  if (J_model <= 0 || J_model > J) return MTR_E_PARAM;
   if (workspace_bytes < mtr_filter_poses_workspace_bytes(P, J, max_per_image)) return MTR_E_WORKSPACE;
   if ((uintptr_t)workspace % 8) return MTR_E_WORKSPACE;
   mtr::FilterArgs fa;
@@ -296,8 +299,6 @@ extern "C" int mtr_filter_poses(const float* poses3d, const float* poses2d, cons
   fa.order_by_score = fp->order_by_score;
   float* ws_mean = (float*)workspace;
   float* ws_sim = ws_mean + (size_t)P * J * 3;
-  const size_t lds = (size_t)4 * ((J + 1) & ~1) * sizeof(float) + (size_t)4 * A * sizeof(double);
-  if (lds > 48 * 1024) return MTR_E_SHAPE;
   MTR_CLEAR_STALE();
   hipLaunchKernelGGL(mtr::pose_filter_kernel, dim3(n_images), dim3(256), lds, (hipStream_t)stream,
                      poses3d, poses2d, boxes, row_start, edges, mean_bones, fa, ws_mean, ws_sim,

@@ -730,7 +730,7 @@ def is_pose_plausible(poses, edges, mean_bones, n_joints=None):
     """plausibility_check.py:8-29.  poses [...,J,3]; a pose is implausible when some bone is
     (< 0.1x or > 3x its mean length) AND more than 300 mm off."""
     n_joints = n_joints or poses.shape[-2]
-    bones = joint2bone_mat(edges, n_joints) @ poses[..., :n_joints, :]
+    bones = joint2bone_mat(edges, n_joints).to(poses.dtype) @ poses[..., :n_joints, :]   # (float64 poses stay float64)
     bone_lengths = torch.norm(bones, dim=-1)
     mean_bones = torch.as_tensor(mean_bones, dtype=torch.float32)
     rel = bone_lengths / mean_bones
