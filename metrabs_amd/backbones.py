@@ -200,32 +200,23 @@ class FusedMBConv(nn.Module):
     def _forward_pre(self, x):
         """An armed f32 block.  'k13_pre': the 3x3 convolution alone, then ONE K13 launch that applies its epilogue,
         the project and the skip; 'k20_pre': the same launch on K20, where fold_batchnorm(split_gemm=True) armed the
-        project and K20 takes the tensor.  'k19' (fold_batchnorm(winograd3x3=True)): the 3x3 convolution WITH its
-        epilogue on K19, then the project and the skip as an ordinary call of the project layer -- K13, or K20 under
-        split_gemm (the project's own last_path says which).  With K19 switched off or refusing, a
-        WinogradConv3x3BiasAct in pre_pair[0] is the ConvBiasAct it derives from, and the block takes the other
-        branches.  'k21' (fold_batchnorm(split3x3=True)): as 'k19', a SplitConv3x3BiasAct on K21.  'k22' (fold_batchnorm(strided3x3=True)): the same for a stride-2 first layer, a
-        StridedConv3x3BiasAct, on K22.  'chain': what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
+        project and K20 takes the tensor.  'k21' / 'k19' / 'k22' (a Dense3x3BiasAct first layer, from
+        fold_batchnorm(split3x3 / winograd3x3 / strided3x3=True), that says so): the 3x3 convolution WITH its epilogue
+        on that kernel of DENSE3X3_KERNELS, then the project and the skip as an ordinary call of the project layer --
+        K13, or K20 under split_gemm (the project's own last_path says which).  With the kernel switched off or
+        refusing, such a layer is the ConvBiasAct it derives from, and the block takes the other branches.  'chain':
+        what an unarmed block runs.  The block asks the layers (path(), last_path) and decides
         nothing for them; the tensor without its epilogue goes to the project alone, which applies that epilogue on
         every path, and no tensor passes through two epilogues.  (tests/test_gpu_backbone_option_combos.py runs the
         branches with every option on.)"""
         first, project = self.pre_pair
         c = first.conv
         residual = x if self.residual else None
-        first_path = first.path(x) if isinstance(first, (WinogradConv3x3BiasAct, StridedConv3x3BiasAct)) else None
-        if first_path == 'k21':
-            # (fold_batchnorm(split3x3=True)) K21 applies the 3x3 layer's own epilogue; the project is then an ordinary
-            # call (K13, or K20 under split_gemm; no prologue) with the skip
-            self.last_path = 'k21'
-            return project(first(x), residual=residual)
-        if first_path == 'k19':
-            # K19 applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
+        first_path = first.path(x) if isinstance(first, Dense3x3BiasAct) else None
+        if first_path in DENSE3X3_KERNELS:
+            # the kernel applies the 3x3 layer's own epilogue; the project is then an ordinary call (K13, or K20 under
             # split_gemm; no prologue) with the skip
-            self.last_path = 'k19'
-            return project(first(x), residual=residual)
-        if first_path == 'k22':
-            # the same for a stride-2 expand: K22 with the layer's own epilogue, then the project as an ordinary call
-            self.last_path = 'k22'
+            self.last_path = first_path
             return project(first(x), residual=residual)
         self.last_path = 'chain'
         if not (FusedMBConv.use_k13_pre and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
@@ -473,6 +464,24 @@ EXPAND_DW_KERNELS = {
                  switch='use_k27h', slower='k27h_slower', fn='expand_depthwise16_tiles', strided=True, mean=False),
     'k28h': dict(option='fuse_expand_depthwise5x5', field='hand_k5_to', takes='k28h_takes', switch='use_k28h',
                  slower='k28h_slower', fn='expand_depthwise16_k5', strided=True, mean=True),
+}
+
+# The kernels that run a dense 3x3, padding-1 layer of an f32 copy with its epilogue as one launch, in the order a layer
+# armed for several asks them (Dense3x3BiasAct.path): K21 in front of K19; K22's layers, of stride 2, are disjoint from
+# both.  Per kernel, which is also its last_path: the fold_batchnorm option that replaces the layers, the class they
+# become, which carries the class-wide switch and the list of slower shapes, the packer of the weight and the layer's
+# attribute that keeps the packed weight (a _derived_weight slot, one per kernel), the C library's shape query and the
+# wrapper in kernels, the layer's stride and what Cin must be a multiple of.  THE place that says which goes with which.
+DENSE3X3_KERNELS = {
+    'k21': dict(option='split3x3', cls='SplitConv3x3BiasAct', switch='use_k21', slower='k21_slower',
+                pack='pack_conv3x3_split_weight', slot='_w3s', query='mtr_conv3x3_split_lds_bytes',
+                fn='conv3x3_bias_act_split', stride=1, cin_multiple=8),
+    'k19': dict(option='winograd3x3', cls='WinogradConv3x3BiasAct', switch='use_k19', slower='k19_slower',
+                pack='pack_conv3x3_winograd_weight', slot='_wu', query='mtr_conv3x3_winograd_lds_bytes',
+                fn='conv3x3_winograd_bias_act', stride=1, cin_multiple=4),
+    'k22': dict(option='strided3x3', cls='StridedConv3x3BiasAct', switch='use_k22', slower='k22_slower',
+                pack='pack_conv3x3_strided_weight', slot='_wsd', query='mtr_conv3x3s2_lds_bytes',
+                fn='conv3x3_strided_bias_act', stride=2, cin_multiple=4),
 }
 
 
@@ -843,14 +852,81 @@ class StemConvBiasAct(ConvBiasAct):
         return super().forward(x, residual)
 
 
-class WinogradConv3x3BiasAct(ConvBiasAct):
-    """A folded dense 3x3, stride-1, padding-1 conv + BN (+ activation) of an f32 copy made with
-    fold_batchnorm(winograd3x3=True): the convolution as Winograd F(2x2, 3x3) on the f32 MFMA, "+ bias", the activation
-    and the block's skip as ONE HIP launch (K19, conv3x3_winograd.hip) instead of a MIOpen convolution followed by K10.
-    Same parameters and state_dict keys as the ConvBiasAct it replaces (the transformed weight is derived state, cached
-    per weight storage and version), which it also is for every input K19 does not take -- CPU, channels_last,
-    autocast, a gradient wanted, odd maps, the shapes listed as slower: those run exactly what ConvBiasAct runs."""
+class Dense3x3BiasAct(ConvBiasAct):
+    """What the three classes below share: a folded dense 3x3, padding-1 conv + BN (+ activation) of an f32 copy whose
+    convolution, "+ bias", activation and skip run as ONE HIP launch on a kernel of DENSE3X3_KERNELS instead of a MIOpen
+    convolution followed by K10.  Same parameters and state_dict keys as the ConvBiasAct it replaces (the packed weight
+    is derived state, cached per kernel, weight storage and version), which it also is for every input no armed kernel
+    takes -- CPU, channels_last, autocast, a gradient wanted, the shapes the entry refuses or the class lists as
+    slower: those run exactly what ConvBiasAct runs.  A subclass names its `kernel`, whose row says the rest."""
 
+    kernel = None  # the key of DENSE3X3_KERNELS whose row names this class
+
+    # (last_path: an armed kernel or what ConvBiasAct says)
+
+    @staticmethod
+    def classes():
+        """The classes the table names, in its order."""
+        return tuple(globals()[row['cls']] for row in DENSE3X3_KERNELS.values())
+
+    @classmethod
+    def applies_to(cls, conv):
+        row = DENSE3X3_KERNELS[cls.kernel]
+        return _dense_3x3(conv, strides=((row['stride'],) * 2,)) and conv.in_channels % row['cin_multiple'] == 0
+
+    def armed(self):
+        """The kernels this layer may run, in the table's order."""
+        return (self.kernel,)
+
+    def packed_weight(self, kernel):
+        """The conv's weight as `kernel` reads it (its row's packer in kernels): made on the first forward that runs
+        the kernel and kept in the row's slot as _derived_weight says."""
+        row = DENSE3X3_KERNELS[kernel]
+        held = _derived_weight(getattr(self, row['slot'], None), self.conv.weight, getattr(kernels, row['pack']))
+        setattr(self, row['slot'], held)
+        return held[1]
+
+    def takes(self, kernel, x):
+        """Whether forward(x) may run on `kernel`: the layer is armed for it and its class-wide switch is on, a CUDA
+        NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape the C entry accepts and that is not listed
+        as slower."""
+        row = DENSE3X3_KERNELS[kernel]
+        cls, c = globals()[row['cls']], self.conv
+        if not (kernel in self.armed() and getattr(cls, row['switch']) and not self.emit_mean and x.is_cuda
+                and x.dim() == 4 and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
+                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
+                and _inference_call(c.weight, x=x)):
+            return False
+        B, K, H, W = x.shape
+        if K != c.in_channels or (K, c.out_channels, H, W) in getattr(cls, row['slower']):
+            return False
+        return getattr(_lib.load(), row['query'])(B, K, c.out_channels, H, W) > 0
+
+    def path(self, x, residual=None, pre=None, defer_epilogue=False):
+        """The first armed kernel that takes `x` and whose epilogue can add `residual`, in front of ConvBiasAct's order
+        (which, for a 3x3 layer, says 'library')."""
+        if not defer_epilogue and pre is None:
+            for kernel in self.armed():
+                s = DENSE3X3_KERNELS[kernel]['stride']
+                if self.takes(kernel, x) and _addable(
+                        residual, x, shape=(x.shape[0], self.conv.out_channels, x.shape[2] // s, x.shape[3] // s)):
+                    return kernel
+        return ConvBiasAct.path(self, x, residual, pre, defer_epilogue)
+
+    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
+        kernel = self.path(x, residual, pre, defer_epilogue)
+        if kernel in DENSE3X3_KERNELS:
+            self.last_path = kernel
+            return getattr(kernels, DENSE3X3_KERNELS[kernel]['fn'])(x, self.packed_weight(kernel), self.bias,
+                                                                    self.act_name, residual=residual)
+        return ConvBiasAct.forward(self, x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+
+
+class WinogradConv3x3BiasAct(Dense3x3BiasAct):
+    """A stride-1 layer with Cin % 4 == 0 of a copy made with fold_batchnorm(winograd3x3=True): Winograd F(2x2, 3x3) on
+    the f32 MFMA (K19, conv3x3_winograd.hip; the weight as [16, Cout, Cin], last_path 'k19')."""
+
+    kernel = 'k19'
     # class-wide switch (tests and A/B runs): the library path everywhere
     use_k19 = True
     # (Cin, Cout, H, W) of the input where K19 (for the expand of a FusedMBConv: K19 + the plain K13 project) was not
@@ -858,58 +934,21 @@ class WinogradConv3x3BiasAct(ConvBiasAct):
     # batch 64 at 256 px, EfficientNetV2-L batch 32 at 384 px; DESIGN.md section 22, profiles/r18a_conv3x3_ab_winograd_*.jsonl)
     k19_slower = frozenset({(512, 512, 8, 8)})
 
-    def __init__(self, conv, bias, act):
-        super().__init__(conv, bias, act)  # (last_path: 'k19' or 'library')
-        self._wu = None
-
-    @staticmethod
-    def applies_to(conv):
-        return _dense_3x3(conv, strides=((1, 1),)) and conv.in_channels % 4 == 0
-
     def weight_u(self):
-        """The conv's weight transformed for K19 ([16, Cout, Cin], kernels.pack_conv3x3_winograd_weight): made on the
-        first K19 forward and kept as _derived_weight says."""
-        self._wu = _derived_weight(self._wu, self.conv.weight, kernels.pack_conv3x3_winograd_weight)
-        return self._wu[1]
+        return self.packed_weight('k19')
 
     def k19_takes(self, x):
-        """Whether forward(x) runs on K19: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
-        the C entry accepts and that is not listed as slower."""
-        c = self.conv
-        if not (WinogradConv3x3BiasAct.use_k19 and not self.emit_mean and x.is_cuda and x.dim() == 4
-                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
-                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
-                and _inference_call(c.weight, x=x)):
-            return False
-        B, K, H, W = x.shape
-        if K != c.in_channels or (K, c.out_channels, H, W) in WinogradConv3x3BiasAct.k19_slower:
-            return False
-        return _lib.load().mtr_conv3x3_winograd_lds_bytes(B, K, c.out_channels, H, W) > 0
-
-    def path(self, x, residual=None, pre=None, defer_epilogue=False):
-        """'k19' in front of ConvBiasAct's order (which, for a 3x3 layer, says 'library')."""
-        if not defer_epilogue and pre is None and self.k19_takes(x) and _addable(
-                residual, x, shape=(x.shape[0], self.conv.out_channels) + x.shape[2:]):
-            return 'k19'
-        return super().path(x, residual, pre, defer_epilogue)
-
-    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
-        if self.path(x, residual, pre, defer_epilogue) == 'k19':
-            self.last_path = 'k19'
-            return kernels.conv3x3_winograd_bias_act(x, self.weight_u(), self.bias, self.act_name, residual=residual)
-        return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+        return self.takes('k19', x)
 
 
 class SplitConv3x3BiasAct(WinogradConv3x3BiasAct):
-    """A folded dense 3x3, stride-1, padding-1 conv + BN (+ activation) with Cin % 8 == 0 of an f32 copy made with
-    fold_batchnorm(split3x3=True): the convolution on the bf16 matrix cores from operands split into three bf16 pieces
-    each (K20's arithmetic), "+ bias", the activation and the block's skip as ONE HIP launch (K21, conv3x3_split.hip)
-    instead of a MIOpen convolution followed by K10.  Same parameters and state_dict keys as the ConvBiasAct it
-    replaces (the split weight is derived state, cached per weight storage and version).  It derives from
-    WinogradConv3x3BiasAct so that one layer can hold both options: `winograd` says whether winograd3x3 was on too.
-    Where K21 refuses the input or lists the shape, the layer runs K19 if `winograd` and K19 takes it, and exactly what
-    ConvBiasAct runs everywhere else -- CPU, channels_last, autocast, a gradient wanted, W % 4 != 0."""
+    """A stride-1 layer with Cin % 8 == 0 of a copy made with fold_batchnorm(split3x3=True): the convolution on the bf16
+    matrix cores from operands split into three bf16 pieces each, K20's arithmetic (K21, conv3x3_split.hip; the weight
+    as [3, Cout, 3, 3, Cp] bf16, last_path 'k21').  It derives from WinogradConv3x3BiasAct so that one layer can hold
+    both options: `winograd` says whether winograd3x3 was on too.  Where K21 refuses the input or lists the shape, the
+    layer runs K19 if `winograd` and K19 takes it, and exactly what ConvBiasAct runs everywhere else."""
 
+    kernel = 'k21'
     # class-wide switch (tests and A/B runs): what the copy without split3x3 runs, everywhere
     use_k21 = True
     # (Cin, Cout, H, W) of the input where K21 (for the expand of a FusedMBConv: K21 + the plain K13 project) was not
@@ -920,111 +959,35 @@ class SplitConv3x3BiasAct(WinogradConv3x3BiasAct):
     k21_slower = frozenset({(256, 256, 16, 16), (512, 512, 8, 8)})
 
     def __init__(self, conv, bias, act, winograd=False):
-        super().__init__(conv, bias, act)  # (last_path: 'k21', 'k19' or 'library')
+        super().__init__(conv, bias, act)
         self.winograd = bool(winograd)
-        self._w3s = None
 
-    @staticmethod
-    def applies_to(conv):
-        return _dense_3x3(conv, strides=((1, 1),)) and conv.in_channels % 8 == 0
+    def armed(self):
+        return ('k21', 'k19') if self.winograd else ('k21',)
 
     def weight_split3(self):
-        """The conv's weight split for K21 ([3, Cout, 3, 3, Cp] bf16, kernels.pack_conv3x3_split_weight): made on the
-        first K21 forward and kept as _derived_weight says."""
-        self._w3s = _derived_weight(self._w3s, self.conv.weight, kernels.pack_conv3x3_split_weight)
-        return self._w3s[1]
-
-    def k19_takes(self, x):
-        """K19 only where winograd3x3 was on as well."""
-        return self.winograd and super().k19_takes(x)
+        return self.packed_weight('k21')
 
     def k21_takes(self, x):
-        """Whether forward(x) runs on K21: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
-        the C entry accepts and that is not listed as slower."""
-        c = self.conv
-        if not (SplitConv3x3BiasAct.use_k21 and not self.emit_mean and x.is_cuda and x.dim() == 4
-                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
-                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
-                and _inference_call(c.weight, x=x)):
-            return False
-        B, K, H, W = x.shape
-        if K != c.in_channels or (K, c.out_channels, H, W) in SplitConv3x3BiasAct.k21_slower:
-            return False
-        return _lib.load().mtr_conv3x3_split_lds_bytes(B, K, c.out_channels, H, W) > 0
-
-    def path(self, x, residual=None, pre=None, defer_epilogue=False):
-        """'k21' in front of WinogradConv3x3BiasAct's order ('k19' where winograd3x3 armed it too, then ConvBiasAct's,
-        which for a 3x3 layer says 'library')."""
-        if not defer_epilogue and pre is None and self.k21_takes(x) and _addable(
-                residual, x, shape=(x.shape[0], self.conv.out_channels) + x.shape[2:]):
-            return 'k21'
-        return super().path(x, residual, pre, defer_epilogue)
-
-    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
-        path = self.path(x, residual, pre, defer_epilogue)
-        if path == 'k21':
-            self.last_path = 'k21'
-            return kernels.conv3x3_bias_act_split(x, self.weight_split3(), self.bias, self.act_name, residual=residual)
-        if path == 'k19':
-            self.last_path = 'k19'
-            return kernels.conv3x3_winograd_bias_act(x, self.weight_u(), self.bias, self.act_name, residual=residual)
-        return ConvBiasAct.forward(self, x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+        return self.takes('k21', x)
 
 
-class StridedConv3x3BiasAct(ConvBiasAct):
-    """A folded dense 3x3, stride-2, padding-1 conv + BN (+ activation) with Cin % 4 == 0 of an f32 copy made with
-    fold_batchnorm(strided3x3=True): the convolution as an implicit GEMM on the f32 MFMA, "+ bias" and the activation
-    as ONE HIP launch (K22, conv3x3_strided.hip) instead of a MIOpen convolution followed by K10.  Same parameters and
-    state_dict keys as the ConvBiasAct it replaces (the packed weight is derived state, cached per weight storage and
-    version), which it also is for every input K22 does not take -- CPU, channels_last, autocast, a gradient wanted,
-    odd maps, the shapes listed as slower: those run exactly what ConvBiasAct runs."""
+class StridedConv3x3BiasAct(Dense3x3BiasAct):
+    """A stride-2 layer with Cin % 4 == 0 of a copy made with fold_batchnorm(strided3x3=True): an implicit GEMM on the
+    f32 MFMA (K22, conv3x3_strided.hip; the weight as [Cin / 4, Cout, 3, 3, 4], last_path 'k22')."""
 
+    kernel = 'k22'
     # class-wide switch (tests and A/B runs): the library path everywhere
     use_k22 = True
     # (Cin, Cout, H, W) of the input where K22 (for the expand of a FusedMBConv: K22 + the plain K13 project) was not
     # ahead of the default copy's path in every round of tools/conv3x3_ab.py --dtype f32 (DESIGN.md section 28)
     k22_slower = frozenset()
 
-    def __init__(self, conv, bias, act):
-        super().__init__(conv, bias, act)  # (last_path: 'k22' or 'library')
-        self._wsd = None
-
-    @staticmethod
-    def applies_to(conv):
-        return _dense_3x3(conv, strides=((2, 2),)) and conv.in_channels % 4 == 0
-
     def weight_s(self):
-        """The conv's weight permuted for K22 ([Cin / 4, Cout, 3, 3, 4], kernels.pack_conv3x3_strided_weight): made on
-        the first K22 forward and kept as _derived_weight says."""
-        self._wsd = _derived_weight(self._wsd, self.conv.weight, kernels.pack_conv3x3_strided_weight)
-        return self._wsd[1]
+        return self.packed_weight('k22')
 
     def k22_takes(self, x):
-        """Whether forward(x) runs on K22: a CUDA NCHW-contiguous f32 input, autocast off, no gradient wanted, a shape
-        the C entry accepts and that is not listed as slower."""
-        c = self.conv
-        if not (StridedConv3x3BiasAct.use_k22 and not self.emit_mean and x.is_cuda and x.dim() == 4
-                and x.dtype == torch.float32 and c.weight.dtype == torch.float32 and c.weight.is_cuda
-                and c.bias is None and x.is_contiguous() and x.data_ptr() % 16 == 0
-                and _inference_call(c.weight, x=x)):
-            return False
-        B, K, H, W = x.shape
-        if K != c.in_channels or (K, c.out_channels, H, W) in StridedConv3x3BiasAct.k22_slower:
-            return False
-        return _lib.load().mtr_conv3x3s2_lds_bytes(B, K, c.out_channels, H, W) > 0
-
-    def path(self, x, residual=None, pre=None, defer_epilogue=False):
-        """'k22' in front of ConvBiasAct's order (which, for a 3x3 layer, says 'library')."""
-        if not defer_epilogue and pre is None and self.k22_takes(x) and _addable(
-                residual, x, shape=(x.shape[0], self.conv.out_channels, x.shape[2] // 2, x.shape[3] // 2)):
-            return 'k22'
-        return super().path(x, residual, pre, defer_epilogue)
-
-    def forward(self, x, residual=None, defer_epilogue=False, pre=None):
-        if self.path(x, residual, pre, defer_epilogue) == 'k22':
-            self.last_path = 'k22'
-            return kernels.conv3x3_strided_bias_act(x, self.weight_s(), self.bias, self.act_name, residual=residual)
-        return super().forward(x, residual=residual, defer_epilogue=defer_epilogue, pre=pre)
+        return self.takes('k22', x)
 
 
 class DepthwiseBiasAct(nn.Module):
@@ -1348,52 +1311,34 @@ def _wire_squeeze_excite(folded):
             prev.gate_to = (nxt[0],)
 
 
-def _replace_winograd(folded):
-    """winograd3x3: every dense 3x3, stride-1, padding-1, ungrouped ConvBiasAct with Cin % 4 == 0 that emits no mean
-    becomes a WinogradConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L, 13 of ResNet-18, none of MobileNetV3.
-    Such a layer runs Winograd F(2x2, 3x3) on the f32 MFMA with "+ bias", the activation and the block's skip in one
-    launch (K19, .last_path 'k19') where that kernel takes the input and the shape is not in
-    WinogradConv3x3BiasAct.k19_slower, and exactly what ConvBiasAct runs everywhere else.  An armed FusedMBConv expand
-    block runs K19 with its own epilogue and then the project as a plain K13 call -- a plain K20 call with
-    split_gemm=True -- (block .last_path 'k19').  Results differ from the default copy's by rounding (both are Winograd
-    evaluations with different summation orders)."""
-    _replace_conv_bias_act(folded, WinogradConv3x3BiasAct)
-
-
-def _replace_split3x3(folded, winograd3x3):
-    """split3x3: every dense 3x3, stride-1, padding-1, ungrouped ConvBiasAct with Cin % 8 == 0 that emits no mean
-    becomes a SplitConv3x3BiasAct: 8 layers of EfficientNetV2-S, 16 of -L, 13 of ResNet-18, none of MobileNetV3.  Such
-    a layer runs on the bf16 matrix cores from split operands, with "+ bias", the activation and the block's skip in
-    one launch (K21, .last_path 'k21') where that kernel takes the input and the shape is not in
-    SplitConv3x3BiasAct.k21_slower.  Everywhere else it runs what the copy without split3x3 runs: K19 where
-    `winograd3x3` is on as well and K19 takes the tensor ('k19'), else exactly what ConvBiasAct runs.  An armed
-    FusedMBConv expand block runs K21 with its own epilogue and then the project as a plain K13 call -- a plain K20
-    call with split_gemm=True -- (block .last_path 'k21').  f32-grade against fp64 but not the library's bits.  Runs
-    in front of _replace_winograd, which then finds these layers taken."""
-    for blk in _replace_conv_bias_act(folded, SplitConv3x3BiasAct):
-        blk[0].winograd = bool(winograd3x3)
-
-
-def _replace_strided3x3(folded):
-    """strided3x3: every dense 3x3, stride-2, padding-1, ungrouped ConvBiasAct with Cin % 4 == 0 that emits no mean
-    becomes a StridedConv3x3BiasAct: 2 layers of EfficientNetV2-S, 2 of -L, 3 of ResNet-18, none of MobileNetV3 (the
-    stems have Cin = 3 and stay K17's).  Such a layer runs as an implicit GEMM on the f32 MFMA with "+ bias" and the
-    activation in one launch (K22, .last_path 'k22') where that kernel takes the input and the shape is not in
-    StridedConv3x3BiasAct.k22_slower, and exactly what ConvBiasAct runs everywhere else.  An armed FusedMBConv expand
-    block runs K22 with its own epilogue and then the project as a plain K13 call -- a plain K20 call with
-    split_gemm=True -- (block .last_path 'k22').  Results differ from the default copy's by rounding (another
-    summation order)."""
-    _replace_conv_bias_act(folded, StridedConv3x3BiasAct)
+def _replace_dense3x3(folded, options):
+    """split3x3, winograd3x3, strided3x3: every dense 3x3, padding-1, ungrouped ConvBiasAct that emits no mean, of the
+    stride and with the Cin multiple of the option's row of DENSE3X3_KERNELS, becomes that row's class, in the table's
+    order -- so the split layers are taken when winograd3x3 looks for its own, and `winograd` on them says whether it
+    was on as well.  Stride 1: 8 layers of EfficientNetV2-S, 16 of -L, 13 of ResNet-18, none of MobileNetV3 (every
+    such layer has Cin % 8 == 0).  Stride 2: 2 of EfficientNetV2-S, 2 of -L, 3 of ResNet-18, none of MobileNetV3 (the
+    stems have Cin = 3 and stay K17's).  Such a layer runs the convolution, "+ bias", the activation and the block's
+    skip in one launch (.last_path 'k21', 'k19' or 'k22') where an armed kernel takes the input and the shape is not
+    in its class's list of slower shapes -- a split layer K21, else K19 where winograd3x3 is on too -- and exactly
+    what ConvBiasAct runs everywhere else.  An armed FusedMBConv expand block runs that kernel with its own epilogue
+    and then the project as a plain K13 call -- a plain K20 call with split_gemm=True -- (block .last_path the same).
+    K19 and K22 differ from the default copy's results by rounding (other summation orders); K21 is f32-grade against
+    fp64 but not the library's bits."""
+    for row in DENSE3X3_KERNELS.values():
+        if options[row['option']]:
+            for blk in _replace_conv_bias_act(folded, globals()[row['cls']]):
+                if isinstance(blk[0], SplitConv3x3BiasAct):
+                    blk[0].winograd = bool(options['winograd3x3'])
 
 
 def _arm_pre_pairs(folded):
-    """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the WinogradConv3x3BiasAct,
-    SplitConv3x3BiasAct or StridedConv3x3BiasAct that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3 layer's K10 pass is left out
+    """An f32 copy: every FusedMBConv whose block is exactly a dense 3x3 ConvBiasAct (or the class of
+    Dense3x3BiasAct.classes() that replaced it) and a 1x1 ConvBiasAct project without activation is armed: the 3x3
+    layer's K10 pass is left out
     and applied by the project's K13 launch as it stages its input (FusedMBConv.pre_pair, .last_path 'k13_pre'), with
     the bits of the chain, which runs wherever K13 does not take the tensor.  Same module tree, same state_dict."""
     for m in folded.modules():
-        pair = _expand_and_project(m, (ConvBiasAct, WinogradConv3x3BiasAct, SplitConv3x3BiasAct,
-                                       StridedConv3x3BiasAct))
+        pair = _expand_and_project(m, (ConvBiasAct,) + Dense3x3BiasAct.classes())
         if pair:
             m.pre_pair = pair
 
@@ -1533,15 +1478,13 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     (_arm_block_depthwise).
     deep_projects=True (needs a 16-bit dtype): the deep project convolutions on K13h's deep-K configuration
     (_arm_deep_projects).
-    winograd3x3=True (needs fused_epilogue=True and an f32 copy, i.e. no dtype -- K14h serves the 16-bit copies): the
-    dense 3x3 stride-1 layers as Winograd on the f32 MFMA, K19 (_replace_winograd).
+    winograd3x3=True, strided3x3=True, split3x3=True (each needs fused_epilogue=True and an f32 copy, i.e. no dtype --
+    K14h serves the 16-bit copies): the dense 3x3 layers on the kernels of DENSE3X3_KERNELS (_replace_dense3x3) --
+    stride 1 with Cin % 4 == 0 as Winograd on the f32 MFMA, K19; stride 2 with Cin % 4 == 0 as an implicit GEMM on
+    the f32 MFMA, K22; stride 1 with Cin % 8 == 0 on the bf16 matrix cores by operand split, K21.  With split3x3 and
+    winograd3x3 both on the layers are SplitConv3x3BiasAct and run K21 where it takes the tensor, K19 where K21 refuses
+    or lists the shape and K19 takes it, the library path otherwise.
     split_gemm=True (needs fused_epilogue=True and an f32 copy): the f32 1x1 layers on K20 (_arm_split_gemm).
-    strided3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-2 layers with Cin % 4 == 0 as an
-    implicit GEMM on the f32 MFMA, K22 (_replace_strided3x3).
-    split3x3=True (needs fused_epilogue=True and an f32 copy): the dense 3x3 stride-1 layers with Cin % 8 == 0 on the
-    bf16 matrix cores by operand split, K21 (_replace_split3x3).  Together with winograd3x3 the layers are
-    SplitConv3x3BiasAct and run K21 where it takes the tensor, K19 where K21 refuses or lists the shape and K19 takes
-    it, the library path otherwise.
     fuse_expand_depthwise=True (needs a 16-bit dtype): the 1x1 expand and the stride-1 depthwise 3x3 layer of an MBConv
     block as one launch, K25h (_arm_expand_depthwise).
     fuse_expand_depthwise_planes=True (needs a 16-bit dtype): the same pairs as one launch on the planes K25h refuses
@@ -1557,8 +1500,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     each unit of a copy with several options on returns the bits of the copy with that unit's options alone (DESIGN.md
     section 24).  The order of the steps below matters: the references between modules are plain attributes, and a
     module replaced after one was taken leaves it pointing at an object outside the tree.  pre_pair, fused_pair and
-    hand_to are taken after the replacements (WinogradConv3x3BiasAct, StridedConv3x3BiasAct, Conv3x3BiasAct,
-    StemConvBiasAct); mean_from and
+    hand_to are taken after the replacements (Dense3x3BiasAct's classes, Conv3x3BiasAct, StemConvBiasAct); mean_from and
     gate_to before them, at layers no replacement touches in these networks (those that emit a mean; the 1x1 projects).
     tests/test_backbone_option_combos_host.py checks every reference of every combination."""
     import copy
@@ -1583,12 +1525,7 @@ def fold_batchnorm(backbone, fused_epilogue=False, dtype=None, fuse_blocks=False
     if fused_epilogue:
         _fold_paddings(folded)
         _wire_squeeze_excite(folded)
-    if split3x3:
-        _replace_split3x3(folded, winograd3x3)
-    if winograd3x3:
-        _replace_winograd(folded)
-    if strided3x3:
-        _replace_strided3x3(folded)
+    _replace_dense3x3(folded, options)
     if fused_epilogue and dtype is None:
         _arm_pre_pairs(folded)
     if dtype is not None:

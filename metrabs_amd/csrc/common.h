@@ -147,6 +147,43 @@ __device__ __forceinline__ void epilogue_store4(float a0, float a1, float a2, fl
   *reinterpret_cast<float4*>(y + off) = r;
 }
 
+// The operand split of K20 and K21: two f32 -> their three bf16 pieces, packed as pairs (low half = the first value)
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split_bf16x3_pairs(float a, float b, unsigned (&out)[3]) {
+  f32x2_t r = {a, b};
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));  // v_cvt_pk_bf16_f32
+    out[p] = pk;
+    if (p < 2) {  // exact: the remainder of a round-to-nearest has at most 16 significant bits
+      r[0] -= __builtin_bit_cast(float, pk << 16);
+      r[1] -= __builtin_bit_cast(float, pk & 0xffff0000u);
+    }
+  }
+}
+
+// What the f32 dense 3x3 entry points (K19, K21, K22) refuse before they launch, in the order the ABI promises:
+// MTR_E_NULL, the entry's own shape rules (`shape()`: its *_shape call, which also fills its geometry), MTR_E_PARAM
+// for the activation, MTR_E_ALIGN, MTR_E_PARAM for a y that overlaps x or the residual -- y is written while other
+// workgroups still read both (the residual may be x).  plane_in / plane_out: elements of one plane of x / of y.
+template <typename Shape>
+inline int dense3x3_check(const void* x, const void* weight, const float* bias, const void* residual, const void* y,
+                          int act, long long B, int Cin, int Cout, size_t plane_in, size_t plane_out, Shape&& shape) {
+  if (!x || !weight || !bias || !y) return MTR_E_NULL;
+  const int e = shape();
+  if (e != MTR_OK) return e;
+  if (act < kActNone || act > kActHardswish) return MTR_E_PARAM;
+  if (((uintptr_t)x % 16) || ((uintptr_t)weight % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
+      ((uintptr_t)bias % 4))
+    return MTR_E_ALIGN;
+  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)B * Cout * plane_out * sizeof(float);
+  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)B * Cin * plane_in * sizeof(float);
+  const uintptr_t r0 = (uintptr_t)residual, r1 = r0 + (size_t)B * Cout * plane_out * sizeof(float);
+  if (x == y || residual == y || (x0 < y1 && y0 < x1) || (residual && r0 < y1 && y0 < r1)) return MTR_E_PARAM;
+  return MTR_OK;
+}
+
 // Positive sizes, whole 16-byte groups (`group` elements: 4 of f32, 8 of 16 bits) of positions and of k, and every
 // index a kernel forms in 32 bits: what the 1x1 entry points (K13, K13h, K20) refuse as MTR_E_SHAPE.
 inline int conv1x1_shape_check(long long B, int M, int K, int HW, int group) {

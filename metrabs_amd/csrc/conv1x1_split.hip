@@ -49,9 +49,7 @@
 namespace mtr {
 
 typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sp_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kSpBN = 64;                  // columns per workgroup
 constexpr int kSpBK = 32;                  // k per step: one v_mfma_f32_16x16x32_bf16
@@ -63,20 +61,6 @@ constexpr int kSpMaxMT = 4;
 
 // byte offset of (column c, 16-byte slot q = k / 8) inside one piece of a stage
 __device__ __forceinline__ int sp_slot(int c, int q) { return c * 64 + ((q ^ (-(c >> 2))) & 3) * 16; }
-
-// two f32 -> their three bf16 pieces, packed as pairs (low half = the first value)
-__device__ __forceinline__ void sp_split2(float a, float b, unsigned (&out)[3]) {
-  sp_f32x2 r = {a, b};
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(r, sp_bf16x2));  // v_cvt_pk_bf16_f32
-    out[p] = pk;
-    if (p < 2) {  // exact: the remainder of a round-to-nearest has at most 16 significant bits
-      r[0] -= __builtin_bit_cast(float, pk << 16);
-      r[1] -= __builtin_bit_cast(float, pk & 0xffff0000u);
-    }
-  }
-}
 
 template <int MT, int PRE, bool GATE>
 __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
@@ -138,7 +122,7 @@ __global__ __launch_bounds__(kSpNT) void conv1x1_split_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       unsigned pk[3];
-      sp_split2(v[0][i], v[1][i], pk);
+      split_bf16x3_pairs(v[0][i], v[1][i], pk);
 #pragma unroll
       for (int p = 0; p < 3; ++p) *reinterpret_cast<unsigned*>(d + p * kSpPiece + i * 64) = pk[p];
     }

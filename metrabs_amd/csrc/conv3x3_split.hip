@@ -56,9 +56,7 @@
 namespace mtr {
 
 typedef float c3s_f32x16 __attribute__((ext_vector_type(16)));
-typedef float c3s_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 c3s_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c3s_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kC3sCK = 16;          // input channels per chunk: the 16 k of one v_mfma_f32_32x32x16_bf16
 constexpr int kC3sBN = 256;         // output positions per workgroup
@@ -80,20 +78,6 @@ struct C3sGeo {
 
 // byte offset of (halo position p, 16-byte half q) inside one piece
 __device__ __forceinline__ int c3s_slot(int p, int q) { return p * 32 + ((q ^ (p >> 3)) & 1) * 16; }
-
-// two f32 -> their three bf16 pieces, packed as pairs (low half = the first value); K20's sp_split2
-__device__ __forceinline__ void c3s_split2(float a, float b, unsigned (&out)[3]) {
-  c3s_f32x2 r = {a, b};
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(r, c3s_bf16x2));  // v_cvt_pk_bf16_f32
-    out[p] = pk;
-    if (p < 2) {  // exact: the remainder of a round-to-nearest has at most 16 significant bits
-      r[0] -= __builtin_bit_cast(float, pk << 16);
-      r[1] -= __builtin_bit_cast(float, pk & 0xffff0000u);
-    }
-  }
-}
 
 // WM x WN waves (WM WN = 4), each FM x FN tiles of 32 x 32 (channels x positions); WN FN = 4
 template <int WM, int WN, int FM, int FN>
@@ -167,8 +151,8 @@ __global__ __launch_bounds__(256, (FM * FN > 2 ? 1 : 2)) void conv3x3_split_kern
 #pragma unroll
       for (int c = 0; c < 4; ++c) {  // column c of the group: channels 4 cq .. 4 cq + 3 of position p0 + c
         unsigned lo[3], hi[3];
-        c3s_split2(v[0][c], v[1][c], lo);
-        c3s_split2(v[2][c], v[3][c], hi);
+        split_bf16x3_pairs(v[0][c], v[1][c], lo);
+        split_bf16x3_pairs(v[2][c], v[3][c], hi);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(d + p * kPiece + c * 32) = make_uint2(lo[p], hi[p]);
       }
@@ -320,19 +304,11 @@ extern "C" int mtr_conv3x3_bias_act_split(const void* x, const void* w_split, co
                                           int act_code, long long B, int Cin, int Cout, int H, int W, void* y,
                                           mtr_stream_t stream) {
   using namespace mtr;
-  if (!x || !w_split || !bias || !y) return MTR_E_NULL;
   C3sGeo g;
-  const int e = conv3x3_split_shape(g, B, Cin, Cout, H, W);
+  const size_t plane = (size_t)H * W;
+  const int e = dense3x3_check(x, w_split, bias, residual, y, act_code, B, Cin, Cout, plane, plane,
+                               [&] { return conv3x3_split_shape(g, B, Cin, Cout, H, W); });
   if (e != MTR_OK) return e;
-  if (act_code < kActNone || act_code > kActHardswish) return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)w_split % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
-      ((uintptr_t)bias % 4))
-    return MTR_E_ALIGN;
-  // y is written while x and the residual are still read by other workgroups: no overlap (the residual may be x)
-  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)B * Cout * H * W * sizeof(float);
-  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)B * Cin * H * W * sizeof(float);
-  const uintptr_t r0 = (uintptr_t)residual, r1 = r0 + (size_t)B * Cout * H * W * sizeof(float);
-  if (x == y || residual == y || (x0 < y1 && y0 < x1) || (residual && r0 < y1 && y0 < r1)) return MTR_E_PARAM;
   if (B == 0) return MTR_OK;  // nothing to do
   const size_t lds = 2 * 3 * (size_t)g.piece;   // above the 64 KiB a kernel gets by default
   const auto go = [&](auto kern) -> int {

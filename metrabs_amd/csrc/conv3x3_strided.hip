@@ -271,19 +271,10 @@ extern "C" int mtr_conv3x3s2_bias_act(const void* x, const float* w_packed, cons
                                       int act_code, long long B, int Cin, int Cout, int H, int W, void* y,
                                       mtr_stream_t stream) {
   using namespace mtr;
-  if (!x || !w_packed || !bias || !y) return MTR_E_NULL;
   S2Geo g;
-  const int e = conv3x3s2_shape(g, B, Cin, Cout, H, W);
+  const int e = dense3x3_check(x, w_packed, bias, residual, y, act_code, B, Cin, Cout, (size_t)H * W,
+                               (size_t)(H / 2) * (W / 2), [&] { return conv3x3s2_shape(g, B, Cin, Cout, H, W); });
   if (e != MTR_OK) return e;
-  if (act_code < kActNone || act_code > kActHardswish) return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)w_packed % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
-      ((uintptr_t)bias % 4))
-    return MTR_E_ALIGN;
-  // y is written while x and the residual are still read by other workgroups: no overlap
-  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)B * Cout * g.OH * g.OW * sizeof(float);
-  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)B * Cin * H * W * sizeof(float);
-  const uintptr_t r0 = (uintptr_t)residual, r1 = r0 + (size_t)B * Cout * g.OH * g.OW * sizeof(float);
-  if (x == y || residual == y || (x0 < y1 && y0 < x1) || (residual && r0 < y1 && y0 < r1)) return MTR_E_PARAM;
   if (B == 0) return MTR_OK;  // nothing to do
   MTR_CLEAR_STALE();
   const dim3 grid(g.blocks), block(256);

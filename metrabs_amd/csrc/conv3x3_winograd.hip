@@ -241,19 +241,11 @@ extern "C" int mtr_conv3x3_winograd_bias_act(const void* x, const float* weight_
                                              const void* residual, int act, long long B, int Cin, int Cout, int H,
                                              int W, void* y, mtr_stream_t stream) {
   using namespace mtr;
-  if (!x || !weight_u || !bias || !y) return MTR_E_NULL;
   WgGeo g;
-  const int e = conv3x3_winograd_shape(g, B, Cin, Cout, H, W);
+  const size_t plane = (size_t)H * W;
+  const int e = dense3x3_check(x, weight_u, bias, residual, y, act, B, Cin, Cout, plane, plane,
+                               [&] { return conv3x3_winograd_shape(g, B, Cin, Cout, H, W); });
   if (e != MTR_OK) return e;
-  if (act < kActNone || act > kActHardswish) return MTR_E_PARAM;
-  if (((uintptr_t)x % 16) || ((uintptr_t)weight_u % 16) || ((uintptr_t)y % 16) || ((uintptr_t)residual % 16) ||
-      ((uintptr_t)bias % 4))
-    return MTR_E_ALIGN;
-  // y is written while x and the residual are still read by other workgroups: no overlap
-  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)B * Cout * H * W * sizeof(float);
-  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)B * Cin * H * W * sizeof(float);
-  const uintptr_t r0 = (uintptr_t)residual, r1 = r0 + (size_t)B * Cout * H * W * sizeof(float);
-  if (x == y || residual == y || (x0 < y1 && y0 < x1) || (residual && r0 < y1 && y0 < r1)) return MTR_E_PARAM;
   if (B == 0) return MTR_OK;  // nothing to do
   const unsigned blocks = (unsigned)(((long long)g.n_tiles + kWgBN - 1) / kWgBN) * g.m_blocks;
   MTR_CLEAR_STALE();

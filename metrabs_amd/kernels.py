@@ -800,16 +800,20 @@ def conv1x1_supported(x, weight):
 CONV1X1_CONFIGS = {'auto': -1, 'wide': 0, 'square': 1, 'tall': 2, 'deepk': 3, 'stream': 4, 'deep64': 5}
 
 
+def _conv1x1_plan(entry, configs, M, K, HW, B, config):
+    """conv1x1_plan and conv1x1_16_plan: the plan query `entry` of the library, its configuration code as a name of
+    `configs`."""
+    plan = (ctypes.c_int * 4)()
+    check(getattr(_lib.load(), entry)(M, K, HW, B, configs[config], ctypes.addressof(plan)), entry)
+    names = {v: k for k, v in configs.items()}
+    return names[plan[0]], plan[1], plan[2], plan[3]
+
+
 def conv1x1_plan(M, K, HW, B, config='auto'):
     """(configuration name, waves along the channels, channels per workgroup, columns per workgroup) K13 runs a
     shape with: the library's own choice, or what a forced `config` resolves to ('stream' on a shape whose weight does
     not fit LDS: 'tall').  Host only."""
-    import ctypes
-    plan = (ctypes.c_int * 4)()
-    check(_lib.load().mtr_conv1x1_plan(M, K, HW, B, CONV1X1_CONFIGS[config], ctypes.addressof(plan)),
-          'mtr_conv1x1_plan')
-    names = {v: k for k, v in CONV1X1_CONFIGS.items()}
-    return names[plan[0]], plan[1], plan[2], plan[3]
+    return _conv1x1_plan('mtr_conv1x1_plan', CONV1X1_CONFIGS, M, K, HW, B, config)
 
 
 def conv1x1_bias_act(x, w, bias, act, gate=None, residual=None, out=None, config='auto', in_bias=None, in_act=None):
@@ -864,12 +868,7 @@ CONV1X1_16_CONFIGS = {'auto': -1, 'tall': 0, 'square': 1, 'deepk': 2}
 def conv1x1_16_plan(M, K, HW, B, config='auto'):
     """(configuration name, waves along the channels, channels per workgroup, columns per workgroup) K13h runs a
     shape with: the library's own choice, or what a forced `config` resolves to.  Host only."""
-    import ctypes
-    plan = (ctypes.c_int * 4)()
-    check(_lib.load().mtr_conv1x1_plan16(M, K, HW, B, CONV1X1_16_CONFIGS[config], ctypes.addressof(plan)),
-          'mtr_conv1x1_plan16')
-    names = {v: k for k, v in CONV1X1_16_CONFIGS.items()}
-    return names[plan[0]], plan[1], plan[2], plan[3]
+    return _conv1x1_plan('mtr_conv1x1_plan16', CONV1X1_16_CONFIGS, M, K, HW, B, config)
 
 
 def conv1x1_bias_act16(x, w, bias, act, gate=None, residual=None, out=None, config='auto'):
@@ -1051,6 +1050,27 @@ def _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, stride=1, k=3):
     return B, K, Cmid, H, W, w1
 
 
+def _expand_dw16_run(name, entry, x, w1, bias1, act1, w_dw, bias_dw, act2, out, out_hw=lambda H, W: (H, W),
+                     stride=None, k=3, want_mean=None, mapping=None):
+    """The body of the wrapper `name` of the C entry `entry`: the checks above, `out` [B, Cmid, *out_hw(H, W)] and the
+    mean, the call.  What an entry does not have stays None: `stride` (K25h, K26h), `want_mean` (K27h has no mean
+    argument), `mapping` (K27h has no `entry`_opts, which the others take for a mapping other than 'auto')."""
+    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
+    code = -1 if mapping is None else EXPAND_DW16_MAPPINGS[mapping]
+    B, K, Cmid, H, W, w1 = _expand_dw16_check(name, x, w1, bias1, w_dw, bias_dw, 1 if stride is None else stride, k)
+    out = _residual_and_out(name, x, (B, Cmid, *out_hw(H, W)), None, out)
+    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
+    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
+            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
+            *(() if stride is None else (int(stride),)), _ptr(out),
+            *(() if want_mean is None else (None if mean is None else _ptr(mean),)), current_stream_ptr(x.device))
+    if code < 0:
+        check(getattr(_lib.load(), entry)(*args), entry)
+    else:
+        check(getattr(_lib.load(), entry + '_opts')(*args, code), entry + '_opts')
+    return (out, mean) if want_mean else out
+
+
 def expand_depthwise16_supported(x, w1):
     """Whether mtr_expand_dw16 takes this input: f16 or bf16 x and 1x1 weight of one dtype, x NCHW-contiguous, both
     16-byte aligned, Cin a multiple of 8, an [.., H, W] plane K11 runs on its stride-1 block kernel
@@ -1069,19 +1089,8 @@ def expand_depthwise16(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean=False,
     conv1x1_bias_act16 followed by depthwise3x3_bias_act(.., 1, 1, want_mean=True) (the same on every call and graph
     replay, and for every `mapping`: a key of EXPAND_DW16_MAPPINGS).  What the kernel does not take raises
     (expand_depthwise16_supported asks first); there is no fallback in here."""
-    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
-    code = EXPAND_DW16_MAPPINGS[mapping]
-    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16', x, w1, bias1, w_dw, bias_dw)
-    out = _residual_and_out('expand_depthwise16', x, (B, Cmid, H, W), None, out)
-    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
-    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
-            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
-            _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
-    if code < 0:
-        check(_lib.load().mtr_expand_dw16(*args), 'mtr_expand_dw16')
-    else:
-        check(_lib.load().mtr_expand_dw16_opts(*args, code), 'mtr_expand_dw16_opts')
-    return (out, mean) if want_mean else out
+    return _expand_dw16_run('expand_depthwise16', 'mtr_expand_dw16', x, w1, bias1, act1, w_dw, bias_dw, act2, out,
+                            want_mean=bool(want_mean), mapping=mapping)
 
 
 # K26h: the same pair on the planes K11 runs on its generic kernel, 24x24 and 12x12 among them
@@ -1103,19 +1112,8 @@ def expand_depthwise16_planes(x, w1, bias1, act1, w_dw, bias_dw, act2, want_mean
     conv1x1_bias_act16 -- the same on every call and graph replay, and for every `mapping` (a key of
     EXPAND_DW16_MAPPINGS).  What the kernel does not take raises (expand_depthwise16_planes_supported asks first);
     there is no fallback in here."""
-    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
-    code = EXPAND_DW16_MAPPINGS[mapping]
-    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_planes', x, w1, bias1, w_dw, bias_dw)
-    out = _residual_and_out('expand_depthwise16_planes', x, (B, Cmid, H, W), None, out)
-    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
-    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
-            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
-            _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
-    if code < 0:
-        check(_lib.load().mtr_expand_dw16_planes(*args), 'mtr_expand_dw16_planes')
-    else:
-        check(_lib.load().mtr_expand_dw16_planes_opts(*args, code), 'mtr_expand_dw16_planes_opts')
-    return (out, mean) if want_mean else out
+    return _expand_dw16_run('expand_depthwise16_planes', 'mtr_expand_dw16_planes', x, w1, bias1, act1, w_dw, bias_dw,
+                            act2, out, want_mean=bool(want_mean), mapping=mapping)
 
 
 # K27h: the same pair on large planes, stride 1 or 2, in bands of output rows and without a mean
@@ -1137,14 +1135,8 @@ def expand_depthwise16_tiles(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, 
     on its generic kernel (at stride 1 also the bits of depthwise3x3_blocks_bias_act behind conv1x1_bias_act16), the
     same on every call and graph replay.  What the kernel does not take raises (expand_depthwise16_tiles_supported
     asks first); there is no fallback in here."""
-    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
-    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_tiles', x, w1, bias1, w_dw, bias_dw, stride)
-    out = _residual_and_out('expand_depthwise16_tiles', x, (B, Cmid, H // stride, W // stride), None, out)
-    check(_lib.load().mtr_expand_dw16_tiles(
-        _ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
-        _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
-        int(stride), _ptr(out), current_stream_ptr(x.device)), 'mtr_expand_dw16_tiles')
-    return out
+    return _expand_dw16_run('expand_depthwise16_tiles', 'mtr_expand_dw16_tiles', x, w1, bias1, act1, w_dw, bias_dw,
+                            act2, out, lambda H, W: (H // stride, W // stride), stride)
 
 
 # K28h: the 1x1 expand and the depthwise 5x5 layer behind it (K15), stride 1 or 2, padding 2, with the mean
@@ -1167,20 +1159,9 @@ def expand_depthwise16_k5(x, w1, bias1, act1, w_dw, bias_dw, act2, stride=1, wan
     have the bits of conv1x1_bias_act16 followed by depthwise5x5_bias_act(.., stride, 2, want_mean=True), the same on
     every call and graph replay, and for every `mapping` (a key of EXPAND_DW16_MAPPINGS).  What the kernel does not take
     raises (expand_depthwise16_k5_supported asks first); there is no fallback in here."""
-    require_cuda(x, w1, bias1, w_dw, bias_dw, out)
-    code = EXPAND_DW16_MAPPINGS[mapping]
-    B, K, Cmid, H, W, w1 = _expand_dw16_check('expand_depthwise16_k5', x, w1, bias1, w_dw, bias_dw, stride, k=5)
-    out = _residual_and_out('expand_depthwise16_k5', x, (B, Cmid, (H - 1) // stride + 1, (W - 1) // stride + 1), None,
-                            out)
-    mean = torch.empty(B, Cmid, device=x.device, dtype=torch.float32) if want_mean else None
-    args = (_ptr(x), dtype_code(x.dtype), _ptr(w1.contiguous()), _ptr(bias1.contiguous().float()), ACT_CODES[act1],
-            _ptr(w_dw.contiguous().float()), _ptr(bias_dw.contiguous().float()), ACT_CODES[act2], B, K, Cmid, H, W,
-            int(stride), _ptr(out), None if mean is None else _ptr(mean), current_stream_ptr(x.device))
-    if code < 0:
-        check(_lib.load().mtr_expand_dw16_k5(*args), 'mtr_expand_dw16_k5')
-    else:
-        check(_lib.load().mtr_expand_dw16_k5_opts(*args, code), 'mtr_expand_dw16_k5_opts')
-    return (out, mean) if want_mean else out
+    return _expand_dw16_run('expand_depthwise16_k5', 'mtr_expand_dw16_k5', x, w1, bias1, act1, w_dw, bias_dw, act2,
+                            out, lambda H, W: ((H - 1) // stride + 1, (W - 1) // stride + 1), stride, 5,
+                            bool(want_mean), mapping)
 
 
 # K17: the backbone stem -- Preproc and the dense 3x3 stride-2 Cin = 3 convolution with the K10 epilogue -- as one
@@ -1249,6 +1230,51 @@ def stem_conv_bias_act(x, weight, bias, act, preproc=False, out=None):
     return out
 
 
+# The f32 dense 3x3 kernels K19, K21 and K22: one body for their `_supported` predicates and one for their wrappers.
+# Each names its C entry and its weight rule `fits(w, Cin)`; a wrapper also the words of the rule's refusal and the stride.
+
+def _dense3x3_supported(x, w, fits, query):
+    """CUDA f32 x [B, Cin, H, W], NCHW-contiguous, x and w 16-byte aligned, `fits(w, Cin)`, then the C library's own
+    shape query `query`(B, Cin, Cout, H, W) > 0."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not w.is_cuda or not x.is_contiguous() \
+            or x.data_ptr() % 16 or w.data_ptr() % 16:
+        return False
+    B, K, H, W = x.shape
+    return bool(fits(w, K)) and getattr(_lib.load(), query)(B, K, w.shape[1], H, W) > 0
+
+
+def _dense3x3_bias_act(fn, entry, stride, fits, wanted, x, w, bias, act, residual, out):
+    """The wrapper `fn` of the C entry `entry`: the checks in their order, `out` [B, Cout, H / stride, W / stride], the
+    call.  `wanted` is the packed weight in the words of the refusal, with {K} for Cin.  A wrapper whose weight is f32
+    names x's dtype together with the weight's; one whose weight is bf16 asks f32 of x at once and shows the weight's
+    dtype behind its shape."""
+    require_cuda(x, w, bias, residual)
+    w_f32 = 'bf16' not in wanted
+    if x.dim() != 4 or not x.is_contiguous() or not (w_f32 or x.dtype == torch.float32):
+        raise ValueError(f'{fn}: x must be [B, Cin, H, W]{"" if w_f32 else " f32"}, NCHW-contiguous')
+    if w_f32 and (x.dtype != torch.float32 or w.dtype != torch.float32):
+        raise ValueError(f'{fn}: x and the weight must be f32, got {x.dtype} and {w.dtype}')
+    B, K, H, W = x.shape
+    if not fits(w, K):
+        raise ValueError(f'{fn}: the weight must be {wanted.format(K=K)}, got {tuple(w.shape)}'
+                         + ('' if w_f32 else f' {w.dtype}'))
+    M = w.shape[1]
+    if bias.numel() != M:
+        raise ValueError(f'{fn}: bias has {bias.numel()} elements, expected {M}')
+    if stride == 2 and (H % 2 or W % 2):
+        raise ValueError(f'{fn}: H and W must be even, got {H} x {W}')
+    out = _residual_and_out(fn, x, (B, M, H // stride, W // stride), residual, out,
+                            hw='H, W' if stride == 1 else 'H / 2, W / 2')
+    for t, name in ((x, 'x'), (residual, 'residual')):
+        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
+                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError(f'{fn}: out must not overlap {name}')
+    check(getattr(_lib.load(), entry)(
+        _ptr(x), _ptr(w), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
+        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), entry)
+    return out
+
+
 # K19: a dense 3x3 stride-1 convolution of f32 tensors as Winograd F(2x2, 3x3) on the f32 MFMA, with the K10 epilogue
 # (csrc/conv3x3_winograd.hip)
 
@@ -1269,18 +1295,16 @@ def pack_conv3x3_winograd_weight(weight):
     return u.reshape(16, weight.shape[0], weight.shape[1]).float().contiguous()
 
 
+def _conv3x3_winograd_weight_fits(w_u, K):
+    return w_u.dim() == 3 and w_u.dtype == torch.float32 and w_u.shape[0] == 16 and w_u.shape[2] == K \
+        and w_u.is_contiguous()
+
+
 def conv3x3_winograd_supported(x, w_u):
     """Whether mtr_conv3x3_winograd_bias_act takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
     aligned, w_u [16, Cout, Cin] f32 contiguous (pack_conv3x3_winograd_weight), H even, W and Cin multiples of 4 (its
     MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
-    if x.dim() != 4 or w_u.dim() != 3 or x.dtype != torch.float32 or w_u.dtype != torch.float32 \
-            or not x.is_cuda or not w_u.is_cuda or not x.is_contiguous() or not w_u.is_contiguous() \
-            or x.data_ptr() % 16 or w_u.data_ptr() % 16:
-        return False
-    B, K, H, W = x.shape
-    if w_u.shape[0] != 16 or w_u.shape[2] != K:
-        return False
-    return _lib.load().mtr_conv3x3_winograd_lds_bytes(B, K, w_u.shape[1], H, W) > 0
+    return _dense3x3_supported(x, w_u, _conv3x3_winograd_weight_fits, 'mtr_conv3x3_winograd_lds_bytes')
 
 
 def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
@@ -1288,27 +1312,9 @@ def conv3x3_winograd_bias_act(x, w_u, bias, act, residual=None, out=None):
     x [B, Cin, H, W] NCHW-contiguous, w_u [16, Cout, Cin] (pack_conv3x3_winograd_weight), bias [Cout] f32, residual
     [B, Cout, H, W] f32 or None (it may be x).  Winograd F(2x2, 3x3) with f32 MFMA chains in a fixed order: the same
     bits on every call and graph replay."""
-    require_cuda(x, w_u, bias, residual)
-    if x.dim() != 4 or not x.is_contiguous():
-        raise ValueError('conv3x3_winograd_bias_act: x must be [B, Cin, H, W], NCHW-contiguous')
-    if x.dtype != torch.float32 or w_u.dtype != torch.float32:
-        raise ValueError(f'conv3x3_winograd_bias_act: x and the weight must be f32, got {x.dtype} and {w_u.dtype}')
-    B, K, H, W = x.shape
-    if w_u.dim() != 3 or w_u.shape[0] != 16 or w_u.shape[2] != K or not w_u.is_contiguous():
-        raise ValueError(f'conv3x3_winograd_bias_act: the weight must be transformed [16, Cout, {K}] and contiguous, '
-                         f'got {tuple(w_u.shape)}')
-    M = w_u.shape[1]
-    if bias.numel() != M:
-        raise ValueError(f'conv3x3_winograd_bias_act: bias has {bias.numel()} elements, expected {M}')
-    out = _residual_and_out('conv3x3_winograd_bias_act', x, (B, M, H, W), residual, out)
-    for t, name in ((x, 'x'), (residual, 'residual')):
-        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
-                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
-            raise ValueError(f'conv3x3_winograd_bias_act: out must not overlap {name}')
-    check(_lib.load().mtr_conv3x3_winograd_bias_act(
-        _ptr(x), _ptr(w_u), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
-        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3_winograd_bias_act')
-    return out
+    return _dense3x3_bias_act('conv3x3_winograd_bias_act', 'mtr_conv3x3_winograd_bias_act', 1,
+                              _conv3x3_winograd_weight_fits, 'transformed [16, Cout, {K}] and contiguous',
+                              x, w_u, bias, act, residual, out)
 
 
 # K22: a dense 3x3 stride-2 convolution of f32 tensors as an implicit GEMM on the f32 MFMA, with the K10 epilogue
@@ -1327,18 +1333,16 @@ def pack_conv3x3_strided_weight(weight):
     return weight.detach().reshape(M, K // 4, 4, 3, 3).permute(1, 0, 3, 4, 2).contiguous()
 
 
+def _conv3x3_strided_weight_fits(w_packed, K):
+    return w_packed.dim() == 5 and w_packed.dtype == torch.float32 and K % 4 == 0 \
+        and tuple(w_packed.shape[2:]) == (3, 3, 4) and w_packed.shape[0] == K // 4 and w_packed.is_contiguous()
+
+
 def conv3x3_strided_supported(x, w_packed):
     """Whether mtr_conv3x3s2_bias_act takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
     aligned, w_packed [Cin / 4, Cout, 3, 3, 4] f32 contiguous (pack_conv3x3_strided_weight), Cin a multiple of 4, H and
     W even, W / 2 a multiple of 4 (its MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
-    if x.dim() != 4 or w_packed.dim() != 5 or x.dtype != torch.float32 or w_packed.dtype != torch.float32 \
-            or not x.is_cuda or not w_packed.is_cuda or not x.is_contiguous() or not w_packed.is_contiguous() \
-            or x.data_ptr() % 16 or w_packed.data_ptr() % 16:
-        return False
-    B, K, H, W = x.shape
-    if K % 4 or tuple(w_packed.shape[2:]) != (3, 3, 4) or w_packed.shape[0] != K // 4:
-        return False
-    return _lib.load().mtr_conv3x3s2_lds_bytes(B, K, w_packed.shape[1], H, W) > 0
+    return _dense3x3_supported(x, w_packed, _conv3x3_strided_weight_fits, 'mtr_conv3x3s2_lds_bytes')
 
 
 def conv3x3_strided_bias_act(x, w_packed, bias, act, residual=None, out=None):
@@ -1346,35 +1350,25 @@ def conv3x3_strided_bias_act(x, w_packed, bias, act, residual=None, out=None):
     x [B, Cin, H, W] NCHW-contiguous, w_packed [Cin / 4, Cout, 3, 3, 4] (pack_conv3x3_strided_weight), bias [Cout] f32,
     residual [B, Cout, H / 2, W / 2] f32 or None.  One f32 fma chain per output element in a fixed order of (ci, ky,
     kx): the same bits on every call and graph replay, for any batch size."""
-    require_cuda(x, w_packed, bias, residual)
-    if x.dim() != 4 or not x.is_contiguous():
-        raise ValueError('conv3x3_strided_bias_act: x must be [B, Cin, H, W], NCHW-contiguous')
-    if x.dtype != torch.float32 or w_packed.dtype != torch.float32:
-        raise ValueError(f'conv3x3_strided_bias_act: x and the weight must be f32, got {x.dtype} and {w_packed.dtype}')
-    B, K, H, W = x.shape
-    if w_packed.dim() != 5 or K % 4 or tuple(w_packed.shape[2:]) != (3, 3, 4) or w_packed.shape[0] != K // 4 \
-            or not w_packed.is_contiguous():
-        raise ValueError(f'conv3x3_strided_bias_act: the weight must be packed [{K} / 4, Cout, 3, 3, 4] and '
-                         f'contiguous, got {tuple(w_packed.shape)}')
-    M = w_packed.shape[1]
-    if bias.numel() != M:
-        raise ValueError(f'conv3x3_strided_bias_act: bias has {bias.numel()} elements, expected {M}')
-    if H % 2 or W % 2:
-        raise ValueError(f'conv3x3_strided_bias_act: H and W must be even, got {H} x {W}')
-    out = _residual_and_out('conv3x3_strided_bias_act', x, (B, M, H // 2, W // 2), residual, out,
-                            hw='H / 2, W / 2')
-    for t, name in ((x, 'x'), (residual, 'residual')):
-        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
-                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
-            raise ValueError(f'conv3x3_strided_bias_act: out must not overlap {name}')
-    check(_lib.load().mtr_conv3x3s2_bias_act(
-        _ptr(x), _ptr(w_packed), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
-        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3s2_bias_act')
-    return out
+    return _dense3x3_bias_act('conv3x3_strided_bias_act', 'mtr_conv3x3s2_bias_act', 2, _conv3x3_strided_weight_fits,
+                              'packed [{K} / 4, Cout, 3, 3, 4] and contiguous', x, w_packed, bias, act, residual, out)
 
 
 # K20: a 1x1 stride-1 convolution of f32 tensors on the bf16 matrix cores, from operands split into three bf16 pieces
 # (csrc/conv1x1_split.hip)
+
+def _split_bf16x3(fn, w):
+    """An f32 tensor as three bf16 pieces: p0 = bf16_rn(w), p1 = bf16_rn(w - p0), p2 = bf16_rn(w - p0 - p1), with
+    p0 + p1 + p2 == w bit for bit, asserted in the name of the packer `fn`."""
+    w0 = w.to(torch.bfloat16)
+    r1 = w - w0.float()
+    w1 = r1.to(torch.bfloat16)
+    w2 = (r1 - w1.float()).to(torch.bfloat16)
+    if not torch.equal(w0.float() + w1.float() + w2.float(), w):
+        raise AssertionError(f'{fn}: the three bf16 pieces do not sum back to the weight '
+                             '(non-finite or subnormal-range values)')
+    return w0, w1, w2
+
 
 def pack_conv1x1_split_weight(weight):
     """The [M, K] (or [M, K, 1, 1]) f32 weight as mtr_conv1x1_bias_act_split takes it: [3, M, Kp] bf16, Kp = K rounded
@@ -1387,14 +1381,7 @@ def pack_conv1x1_split_weight(weight):
         raise ValueError(f'pack_conv1x1_split_weight: expected an f32 weight, got {weight.dtype}')
     w = weight.detach().reshape(weight.shape[0], -1)
     M, K = w.shape
-    w0 = w.to(torch.bfloat16)
-    r1 = w - w0.float()
-    w1 = r1.to(torch.bfloat16)
-    r2 = r1 - w1.float()
-    w2 = r2.to(torch.bfloat16)
-    if not torch.equal(w0.float() + w1.float() + w2.float(), w):
-        raise AssertionError('pack_conv1x1_split_weight: the three bf16 pieces do not sum back to the weight '
-                             '(non-finite or subnormal-range values)')
+    w0, w1, w2 = _split_bf16x3('pack_conv1x1_split_weight', w)
     Kp = (K + 31) // 32 * 32
     out = torch.zeros(3, M, Kp, dtype=torch.bfloat16, device=w.device)
     out[0, :, :K], out[1, :, :K], out[2, :, :K] = w0, w1, w2
@@ -1466,14 +1453,7 @@ def pack_conv3x3_split_weight(weight):
         raise ValueError(f'pack_conv3x3_split_weight: expected an f32 weight, got {weight.dtype}')
     w = weight.detach().permute(0, 2, 3, 1)   # [Cout, 3, 3, Cin]
     M, K = weight.shape[:2]
-    w0 = w.to(torch.bfloat16)
-    r1 = w - w0.float()
-    w1 = r1.to(torch.bfloat16)
-    r2 = r1 - w1.float()
-    w2 = r2.to(torch.bfloat16)
-    if not torch.equal(w0.float() + w1.float() + w2.float(), w):
-        raise AssertionError('pack_conv3x3_split_weight: the three bf16 pieces do not sum back to the weight '
-                             '(non-finite or subnormal-range values)')
+    w0, w1, w2 = _split_bf16x3('pack_conv3x3_split_weight', w)
     Kp = (K + CONV3X3_SPLIT_CHUNK - 1) // CONV3X3_SPLIT_CHUNK * CONV3X3_SPLIT_CHUNK
     out = torch.zeros(3, M, 3, 3, Kp, dtype=torch.bfloat16, device=w.device)
     out[0, ..., :K], out[1, ..., :K], out[2, ..., :K] = w0, w1, w2
@@ -1491,13 +1471,7 @@ def conv3x3_split_supported(x, w_split):
     """Whether mtr_conv3x3_bias_act_split takes this input: CUDA f32 x [B, Cin, H, W], NCHW-contiguous and 16-byte
     aligned, w_split [3, Cout, 3, 3, Cp] bf16 contiguous (pack_conv3x3_split_weight), Cin a multiple of 8, W a multiple
     of 4 (its MTR_E_SHAPE / MTR_E_ALIGN rules, checked without a launch)."""
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not w_split.is_cuda or not x.is_contiguous() \
-            or x.data_ptr() % 16 or w_split.data_ptr() % 16:
-        return False
-    B, K, H, W = x.shape
-    if not _conv3x3_split_weight_fits(w_split, K):
-        return False
-    return _lib.load().mtr_conv3x3_split_lds_bytes(B, K, w_split.shape[1], H, W) > 0
+    return _dense3x3_supported(x, w_split, _conv3x3_split_weight_fits, 'mtr_conv3x3_split_lds_bytes')
 
 
 def conv3x3_bias_act_split(x, w_split, bias, act, residual=None, out=None):
@@ -1506,22 +1480,6 @@ def conv3x3_bias_act_split(x, w_split, bias, act, residual=None, out=None):
     (pack_conv3x3_split_weight), bias [Cout] f32, residual [B, Cout, H, W] f32 or None (it may be x).  The f32 product
     is summed from six bf16 products of the split operands in a fixed order: f32-grade against fp64, the same bits on
     every call and graph replay, for any batch size, but not the bits of the library's convolution."""
-    require_cuda(x, w_split, bias, residual)
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise ValueError('conv3x3_bias_act_split: x must be [B, Cin, H, W] f32, NCHW-contiguous')
-    B, K, H, W = x.shape
-    if not _conv3x3_split_weight_fits(w_split, K):
-        raise ValueError(f'conv3x3_bias_act_split: the weight must be split [3, Cout, 3, 3, Cp] bf16 and contiguous '
-                         f'for {K} input channels (a multiple of 8), got {tuple(w_split.shape)} {w_split.dtype}')
-    M = w_split.shape[1]
-    if bias.numel() != M:
-        raise ValueError(f'conv3x3_bias_act_split: bias has {bias.numel()} elements, expected {M}')
-    out = _residual_and_out('conv3x3_bias_act_split', x, (B, M, H, W), residual, out)
-    for t, name in ((x, 'x'), (residual, 'residual')):
-        if t is not None and t.numel() and out.numel() and t.data_ptr() < out.data_ptr() + out.numel() * 4 \
-                and out.data_ptr() < t.data_ptr() + t.numel() * 4:
-            raise ValueError(f'conv3x3_bias_act_split: out must not overlap {name}')
-    check(_lib.load().mtr_conv3x3_bias_act_split(
-        _ptr(x), _ptr(w_split), _ptr(bias.contiguous().float()), None if residual is None else _ptr(residual),
-        ACT_CODES[act], B, K, M, H, W, _ptr(out), current_stream_ptr(x.device)), 'mtr_conv3x3_bias_act_split')
-    return out
+    return _dense3x3_bias_act('conv3x3_bias_act_split', 'mtr_conv3x3_bias_act_split', 1, _conv3x3_split_weight_fits,
+                              'split [3, Cout, 3, 3, Cp] bf16 and contiguous for {K} input channels (a multiple of 8)',
+                              x, w_split, bias, act, residual, out)
